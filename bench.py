@@ -4,7 +4,9 @@
 One "step" = one forward + backward of the operator (GaussianRasterizer surface) on one synthetic keyframe per
 GPU, 640x480, 500k Gaussians, inputs resident in HBM; with --gpus N > 1 each rank renders its own keyframe of the
 same replicated map and the [P,13] Gaussian-gradient bucket is all-reduced over RCCL (keyframe-sharded BA step,
-gaus_slam_amd/ba_shard.py).  Prints ONE JSON line on rank 0 (contract in the task statement), including
+gaus_slam_amd/ba_shard.py).  Prints ONE JSON line on rank 0.  A plain run measures the
+headline figure alone (setup, clock pre-warm, warm-up, the --steps timed steps); --full adds the cold-start and
+reference-binning legs, per-stage device times and
   roofline     -- dominant kernel: algorithmic bytes / hipEvent-measured launch duration vs 8 TB/s HBM, the HBM bytes
                   of the committed rocprofv3 PMC profile, and the vector-issue ceiling the kernel actually runs against
   cpu_baseline -- the CPU oracle (oracle/, C + OpenMP) timed on this box's host cores on the same workload, and the
@@ -14,6 +16,9 @@ gaus_slam_amd/ba_shard.py).  Prints ONE JSON line on rank 0 (contract in the tas
 workload): replica (1200x680 / 600k), scannetpp (1168x876 / 2M), scannetpp_ref (876x584 / 2M, the reference config's
 render size), b200k (640x480 / 200k), tracking (BASELINE.json configs[2]: one Frontend tracking iteration = fused
 pose-gradient render + tracking loss + Adam on the pose) and mapping (render + mapping loss + backward + fused Adam).
+
+--dump-outputs DIR writes what the last timed step handed its caller (images, loss, gradients) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -114,7 +119,16 @@ def main():
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the cold-start leg (config.cold_value) and the "
                     "reference-binning leg (config.reference_binning_value)")
     ap.add_argument("--json-out", default=None, help="also write the JSON line to this file (profiles/...)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: the cold-start and "
+                    "reference-binning legs, the collective alone (N > 1), per-stage device times, num_rendered, the roofline "
+                    "(with its 1 GiB copy) and the CPU baselines.  Off by default: a plain run sets up, warms up, times --steps "
+                    "steps and prints the result line with these fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "handed its caller (images, loss, gradients) as DIR/<name>.npy in float32; when the arrays would pass "
+                    f"{DUMP_LIMIT_BYTES // 10**6} MB together, each is flattened and cut to a fixed, seeded sample of its elements")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started without a launcher: run the N ranks as a child torch.distributed.run job (nothing here has touched the
@@ -194,6 +208,38 @@ PREWARM_DONE = 0        # steps actually run (reported as config.prewarm_steps)
 
 
 HOST_CPU_FRACTION = None
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together, npy headers included
+
+
+def to_host(arrays):
+    """name -> tensor (any device) -> name -> numpy array in float32 (float64 stays float64), for --dump-outputs."""
+    out = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = torch.as_tensor(t).detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        out[name] = t.contiguous().cpu().numpy()
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes name -> numpy array as out_dir/<name>.npy.  When the arrays pass DUMP_LIMIT_BYTES together, every array is
+    flattened and cut to the same fraction of its elements, taken at sorted positions drawn with a fixed seed: the same
+    arguments give the same positions in every run and every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128  # bytes of npy header per file (numpy pads the header to a multiple of 64; 128 covers these shapes)
+    total = sum(a.nbytes for a in arrays.values())
+    room = DUMP_LIMIT_BYTES - header * len(arrays)
+    frac = 1.0 if total <= room else room / total
+    for name, a in arrays.items():
+        if frac < 1.0:
+            n = a.size
+            k = max(1, int(n * frac))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def timed(one_step, steps, warmup, world, dev, prewarm=True):
@@ -344,6 +390,8 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
     settings = gs_render.settings_from_camera(cam, dev, use_sa=use_sa)
     last = {}
     kf_settings = {}
+    keep = args.dump_outputs is not None  # hold on to what each step hands its caller (the last timed step's is dumped)
+    kept = {}
 
     def render_fn(p, _kf):
         # gradient carrier only: neither the reference's extension (its Python wrapper does not even pass it down,
@@ -352,6 +400,8 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
         pkg = gs_render.render(kf_settings.get(_kf) or settings, p["means3D"], means2D, p["opacities"], colors_precomp=p["colors"],
                                scales=p["scales"], rotations=p["rotations"])
         last["radius"] = pkg["radius"]
+        if keep:
+            kept[_kf] = (pkg["render_color"], pkg["allmap"], pkg["radius"])
         return (pkg["render_color"], pkg["allmap"]), (dcolor, dallmap)
 
     kpg = max(1, args.keyframes_per_gpu)
@@ -371,7 +421,9 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
                                       colors_precomp=p["colors"], scales=p["scales"], rotations=p["rotations"])
         last["radius"] = pkgs[0]["radius"]
         outs, ups = [], []
-        for pk in pkgs:
+        for kf, pk in zip(kfs, pkgs):
+            if keep:
+                kept[kf] = (pk["render_color"], pk["allmap"], pk["radius"])
             outs += [pk["render_color"], pk["allmap"]]
             ups += [dcolor, dallmap]
         return outs, ups
@@ -390,6 +442,8 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
 
     def one_step():
         g = ba.step(keyframes)
+        if keep:
+            kept["grads"] = g
         if args.adam == "torch":
             for n in names:
                 params[n].grad = g[n].reshape(params[n].shape)
@@ -411,16 +465,25 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
         tuned = ba.autotune(keyframes)
     # The driver's protocol as stated (W warm-up steps right after setup, then K timed steps) -- what `--prewarm-steps 0`
     # measures -- runs FIRST, while the card is still in the clocks a fresh process finds it in; it is reported as
-    # config.cold_value.  The headline leg then adds the untimed clock pre-warm (see timed()).
+    # config.cold_value (--full only).  The headline leg then adds the untimed clock pre-warm (see timed()).
     cold_elapsed = None
-    if PREWARM_STEPS > 0 and not args.no_extra_legs:
+    if args.full and PREWARM_STEPS > 0 and not args.no_extra_legs:
         cold_elapsed = timed(one_step, args.steps, args.warmup, world, dev, prewarm=False)
     elapsed = timed(one_step, args.steps, args.warmup, world, dev)
     host_cpu = HOST_CPU_FRACTION
+    if keep and rank == 0:  # the headline leg's last step, before any later leg runs the step again
+        arrays = {}
+        frames_kept = sorted(k for k in kept if isinstance(k, int))
+        for kf in frames_kept:
+            sfx = "" if len(frames_kept) == 1 else f"_kf{kf}"
+            color, allmap, radius = kept[kf]
+            arrays.update({"render_color" + sfx: color, "allmap" + sfx: allmap, "radius" + sfx: radius})
+        arrays.update({"grad_" + n: g for n, g in kept["grads"].items()})
+        dump_outputs(args.dump_outputs, to_host(arrays))
     # The same steps in the contract's binning mode (gs2d_set_reference_binning(1): the reference's 3-sigma tile
     # rectangles, num_rendered and the sorted lists bit-identical to the reference's), on the now warm card.
     ref_elapsed = None
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         from gaus_slam_amd import rasterizer as _rz
         _rz.set_reference_binning(True)
         try:
@@ -430,7 +493,7 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
     frames = args.steps * world * kpg
     ms_per_step = elapsed / args.steps * 1e3
     allreduce_ms = None
-    if _dist_on(world):  # the collective alone, on the same bucket (reported separately)
+    if args.full and _dist_on(world):  # the collective alone, on the same bucket (reported separately)
         torch.cuda.synchronize()
         dist.barrier()
         t0 = time.perf_counter()
@@ -441,37 +504,38 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
     if rank != 0:
         return None
 
-    L = _lib.lib()
-    # ---- per-stage device time via hipEvents on the launch stream (separate, untimed leg)
-    L.gs2d_stage_timing_enable(1)
-    acc = [0.0] * len(STAGES)
-    nrep = 10
-    buf = (C.c_float * len(STAGES))()
-    for _ in range(nrep):
-        ba.local_backward(0)
-        L.gs2d_stage_timing_read(buf)
-        for i in range(len(STAGES)):
-            acc[i] += max(buf[i], 0.0)
-    L.gs2d_stage_timing_enable(0)
-    stage_ms = {n: acc[i] / nrep for i, n in enumerate(STAGES)}
-    visible = int((last["radius"] > 0).sum().item())
-    from gaus_slam_amd import rasterizer
-    with torch.no_grad():
-        e = torch.empty(0, device=dev)
-        count = lambda: rasterizer.rasterize_gaussians(settings.bg, params["means3D"], params["colors"], params["opacities"],
-                                                       params["scales"], params["rotations"], 1.0, e, settings.viewmatrix,
-                                                       settings.projmatrix, settings.tanfovx, settings.tanfovy, H, W, e, 0,
-                                                       settings.campos, use_sa, False, False)[0]
-        R = count()  # instances the timed path handles (footprint binning, the library default)
-        rasterizer.set_reference_binning(True)
-        try:
-            R_ref = count()  # instances of the reference's 3-sigma rectangles, for comparison only
-        finally:
-            rasterizer.set_reference_binning(False)
-    roofline = build_roofline(args, dev, stage_ms, P, R, H * W, ms_per_step)
-    cpu_baseline = None
-    if world == 1 and not args.no_cpu_baseline:
-        cpu_baseline = cpu_baseline_leg(sc, W, H, use_sa)
+    R = R_ref = visible = roofline = cpu_baseline = None
+    if args.full:
+        L = _lib.lib()
+        # ---- per-stage device time via hipEvents on the launch stream (separate, untimed leg)
+        L.gs2d_stage_timing_enable(1)
+        acc = [0.0] * len(STAGES)
+        nrep = 10
+        buf = (C.c_float * len(STAGES))()
+        for _ in range(nrep):
+            ba.local_backward(0)
+            L.gs2d_stage_timing_read(buf)
+            for i in range(len(STAGES)):
+                acc[i] += max(buf[i], 0.0)
+        L.gs2d_stage_timing_enable(0)
+        stage_ms = {n: acc[i] / nrep for i, n in enumerate(STAGES)}
+        visible = int((last["radius"] > 0).sum().item())
+        from gaus_slam_amd import rasterizer
+        with torch.no_grad():
+            e = torch.empty(0, device=dev)
+            count = lambda: rasterizer.rasterize_gaussians(settings.bg, params["means3D"], params["colors"], params["opacities"],
+                                                           params["scales"], params["rotations"], 1.0, e, settings.viewmatrix,
+                                                           settings.projmatrix, settings.tanfovx, settings.tanfovy, H, W, e, 0,
+                                                           settings.campos, use_sa, False, False)[0]
+            R = count()  # instances the timed path handles (footprint binning, the library default)
+            rasterizer.set_reference_binning(True)
+            try:
+                R_ref = count()  # instances of the reference's 3-sigma rectangles, for comparison only
+            finally:
+                rasterizer.set_reference_binning(False)
+        roofline = build_roofline(args, dev, stage_ms, P, R, H * W, ms_per_step)
+        if world == 1 and not args.no_cpu_baseline:
+            cpu_baseline = cpu_baseline_leg(sc, W, H, use_sa)
     return {
         "metric": f"fwd+bwd frames/sec @ {W}x{H}, {P // 1000}k Gaussians", "value": round(frames / elapsed, 3),
         "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_steps": PREWARM_DONE,
@@ -497,7 +561,7 @@ def op_workload(args, dev, P, W, H, regime, use_sa, rank, world):
                    "allreduce_chunks_tuning_ms": {str(k): round(v, 4) for k, v in tuned.items()} or None,
                    "allreduce_tuning_error": tune_error,
                    "host_cpu_fraction": host_cpu,
-                   "launch_ahead": bool(_lib.lib().gs2d_get_launch_ahead())},
+                   "launch_ahead": bool(_lib.lib().gs2d_get_launch_ahead()), "full": args.full},
         "roofline": roofline, "cpu_baseline": cpu_baseline,
     }
 
@@ -514,6 +578,8 @@ def slam_iteration_workload(args, dev, P, W, H, use_sa, rank, world):
     gt_color = torch.rand(H, W, 3, generator=g).to(dev)
     gt_depth = (0.5 + 5 * torch.rand(H, W, 1, generator=g)).to(dev)
     is_tracking = args.workload.startswith("tracking")
+    keep = args.dump_outputs is not None  # hold on to what each iteration hands its caller (the last timed one's is dumped)
+    kept = {}
     if is_tracking:
         sc = make_scene(P, W, H, seed=0, regime="tracking")
         settings = gs_render.settings_from_camera(sc["cam"], dev, use_sa=use_sa)
@@ -532,11 +598,14 @@ def slam_iteration_workload(args, dev, P, W, H, use_sa, rank, world):
             opt.zero_grad(set_to_none=True)
             pkg = tracking.render_tracking(settings, w2c, p["means3D"], p["opacities"], p["colors"], p["scales"], p["rotations"])
             if args.loss_autograd:
-                gl.tracking_loss(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, 0.5, 1.0).backward(one)
+                _loss = gl.tracking_loss(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, 0.5, 1.0)
+                _loss.backward(one)
             else:  # loss value + gradients in one call, the rasterizer's backward seeded directly
                 _loss, g_c, g_a = gl.tracking_loss_and_grads(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, 0.5, 1.0)
                 torch.autograd.backward([pkg["render_color"], pkg["allmap"]], [g_c, g_a])
             opt.step()
+            if keep:
+                kept.update(render_color=pkg["render_color"], allmap=pkg["allmap"], radius=pkg["radius"], loss=_loss)
         step_desc = "pose transform fused into the preprocess + render + fused tracking loss (value + gradients in one call) + pose-only backward + Adam on the pose"
         metric = f"tracking iterations/sec @ {W}x{H}, {P // 1000}k Gaussians"
     else:
@@ -554,46 +623,59 @@ def slam_iteration_workload(args, dev, P, W, H, use_sa, rank, world):
         def loss_fn(q, _kf):
             pk = rasterize(q)
             if args.loss_autograd:
-                return gl.mapping_loss(pk["render_color"], pk["allmap"], gt_color, gt_depth, 0.5, 1.0, 0.1)
+                _loss = gl.mapping_loss(pk["render_color"], pk["allmap"], gt_color, gt_depth, 0.5, 1.0, 0.1)
+                if keep:
+                    kept.update(render_color=pk["render_color"], allmap=pk["allmap"], radius=pk["radius"], loss=_loss)
+                return _loss
             _loss, g_c, g_a = gl.mapping_loss_and_grads(pk["render_color"], pk["allmap"], gt_color, gt_depth, 0.5, 1.0, 0.1)
+            if keep:
+                kept.update(render_color=pk["render_color"], allmap=pk["allmap"], radius=pk["radius"], loss=_loss)
             return (pk["render_color"], pk["allmap"]), (g_c, g_a)
         ba = ba_shard.KeyframeShardedBA(leaves, loss_fn, direct_grads=True)
 
         def one_step():
-            ba.step([0])
+            g = ba.step([0])
             fopt.step(ba.bucket.flat, leaves)
+            if keep:
+                kept.update({"grad_" + n: v for n, v in g.items()})
         step_desc = "render + fused mapping loss (value + gradients in one call) + backward (gradients written into the bucket) + fused Adam over the SoA"
         metric = f"mapping iterations/sec @ {W}x{H}, {P // 1000}k Gaussians"
     elapsed = timed(one_step, args.steps, args.warmup, world, dev)
     host_cpu = HOST_CPU_FRACTION
-    # per-stage device time of the operator's kernels inside the iteration (hipEvents on the launch stream; separate, untimed leg)
-    L = _lib.lib()
-    L.gs2d_stage_timing_enable(1)
-    acc = [0.0] * len(STAGES)
-    buf = (C.c_float * len(STAGES))()
-    for _ in range(10):
-        one_step()
-        L.gs2d_stage_timing_read(buf)
-        for i in range(len(STAGES)):
-            acc[i] += max(buf[i], 0.0)
-    L.gs2d_stage_timing_enable(0)
-    stage_ms = {n: round(acc[i] / 10, 4) for i, n in enumerate(STAGES)}
-    from gaus_slam_amd import rasterizer
-    with torch.no_grad():  # instances the iteration's render handles
-        e = torch.empty(0, device=dev)
-        q = p if is_tracking else leaves
-        kw = dict(pose_Rt=w2c[:3, :4].detach().contiguous()) if is_tracking else {}
-        R = rasterizer.rasterize_gaussians(settings.bg, q["means3D"], q["colors"], q["opacities"], q["scales"], q["rotations"], 1.0, e,
-                                           settings.viewmatrix, settings.projmatrix, settings.tanfovx, settings.tanfovy, H, W, e, 0,
-                                           settings.campos, use_sa, False, False, **kw)[0]
-    roofline = build_roofline(args, dev, stage_ms, sc["means3D"].shape[0], R, H * W, elapsed / args.steps * 1e3,
-                              pose_only=is_tracking)
+    if keep:  # the last timed iteration's outputs; tracking: the pose after its Adam step and the pose gradient
+        if is_tracking:
+            kept.update(w2c=w2c, grad_w2c=w2c.grad)
+        dump_outputs(args.dump_outputs, to_host(kept))
+    R = stage_ms = roofline = None
+    if args.full:
+        # per-stage device time of the operator's kernels inside the iteration (hipEvents on the launch stream; separate, untimed leg)
+        L = _lib.lib()
+        L.gs2d_stage_timing_enable(1)
+        acc = [0.0] * len(STAGES)
+        buf = (C.c_float * len(STAGES))()
+        for _ in range(10):
+            one_step()
+            L.gs2d_stage_timing_read(buf)
+            for i in range(len(STAGES)):
+                acc[i] += max(buf[i], 0.0)
+        L.gs2d_stage_timing_enable(0)
+        stage_ms = {n: round(acc[i] / 10, 4) for i, n in enumerate(STAGES)}
+        from gaus_slam_amd import rasterizer
+        with torch.no_grad():  # instances the iteration's render handles
+            e = torch.empty(0, device=dev)
+            q = p if is_tracking else leaves
+            kw = dict(pose_Rt=w2c[:3, :4].detach().contiguous()) if is_tracking else {}
+            R = rasterizer.rasterize_gaussians(settings.bg, q["means3D"], q["colors"], q["opacities"], q["scales"], q["rotations"], 1.0, e,
+                                               settings.viewmatrix, settings.projmatrix, settings.tanfovx, settings.tanfovy, H, W, e, 0,
+                                               settings.campos, use_sa, False, False, **kw)[0]
+        roofline = build_roofline(args, dev, stage_ms, sc["means3D"].shape[0], R, H * W, elapsed / args.steps * 1e3,
+                                  pose_only=is_tracking)
     return {"metric": metric, "value": round(args.steps / elapsed, 3), "unit": "iterations/s", "n_gpus": 1, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"synthetic {W}x{H} / {P} Gaussians, {args.workload} iteration (BASELINE.json configs[2] loop shape), "
                                    f"use_sa={use_sa}", "step": step_desc, "parallelism": "single GPU", "prewarm_steps": PREWARM_DONE,
-                       "num_rendered": R, "stage_ms": stage_ms, "host_cpu_fraction": host_cpu},
+                       "num_rendered": R, "stage_ms": stage_ms, "host_cpu_fraction": host_cpu, "full": args.full},
             "roofline": roofline, "cpu_baseline": None}
 
 

@@ -3,7 +3,7 @@ numbers are the ones to read, the first also warms the box).  usage: stage_ms.py
 import json, os, subprocess, sys
 extra = sys.argv[2:]
 for rep in range(int(sys.argv[1]) if len(sys.argv) > 1 else 2):
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-extra-legs"] + extra,
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-extra-legs"] + extra,
                          capture_output=True, text=True).stdout
     j = json.loads(out.strip().splitlines()[-1])
     sm = (j.get("roofline") or {}).get("stage_ms") or (j.get("config") or {}).get("stage_ms") or {}

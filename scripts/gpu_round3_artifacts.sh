@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "$PART" = "1" ]; then
-  timeout -k 10 400 python bench.py --json-out $OUT/bench_final.json > $OUT/bench_final.log 2>&1 || true
+  timeout -k 10 400 python bench.py --full --json-out $OUT/bench_final.json > $OUT/bench_final.log 2>&1 || true
   echo "bench done"; tail -c 400 $OUT/bench_final.log
   (cd /tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/trace -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --prewarm-steps 100 --no-cpu-baseline --no-extra-legs > $GRAFT_REPO_ROOT/$OUT/trace.log 2>&1) || true
   echo "trace done"
@@ -23,18 +23,18 @@ if [ "$PART" = "1" ]; then
   head -30 $OUT/summary.txt
 elif [ "$PART" = "2" ]; then
   for w in b200k replica scannetpp scannetpp_ref tracking mapping; do
-    timeout -k 10 300 python bench.py --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_$w.json > $OUT/bench_$w.log 2>&1 || true
+    timeout -k 10 300 python bench.py --full --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_$w.json > $OUT/bench_$w.log 2>&1 || true
     echo "$w: $(python3 -c "import json;d=json.load(open('$OUT/bench_$w.json'));print(d['value'],d['unit'],d['ms_per_step'])" 2>/dev/null)"
   done
   for k in 2 4 8; do
-    timeout -k 10 300 python bench.py --keyframes-per-gpu $k --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_kpg$k.json > $OUT/bench_kpg$k.log 2>&1 || true
+    timeout -k 10 300 python bench.py --full --keyframes-per-gpu $k --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_kpg$k.json > $OUT/bench_kpg$k.log 2>&1 || true
     echo "kpg$k: $(python3 -c "import json;d=json.load(open('$OUT/bench_kpg$k.json'));print(d['value'],d['unit'],d['ms_per_step'])" 2>/dev/null)"
   done
-  timeout -k 10 300 python bench.py --keyframes-per-gpu 4 --no-batch --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_kpg4_nobatch.json > $OUT/bench_kpg4_nobatch.log 2>&1 || true
+  timeout -k 10 300 python bench.py --full --keyframes-per-gpu 4 --no-batch --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_kpg4_nobatch.json > $OUT/bench_kpg4_nobatch.log 2>&1 || true
   timeout -k 10 200 python scripts/dev/batch_host_profile.py 1 2>&1 | grep -E "K=|timeline" > $OUT/timeline_k1.txt || true
   timeout -k 10 200 python scripts/dev/batch_host_profile.py 4 2>&1 | grep -E "K=|timeline" > $OUT/timeline_k4.txt || true
   (cd /tmp && timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --output-format csv -d $GRAFT_REPO_ROOT/$OUT/lds -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --prewarm-steps 20 --no-cpu-baseline --no-extra-legs > $GRAFT_REPO_ROOT/$OUT/lds.log 2>&1) || true
-  timeout -k 10 300 python bench.py --adam fused --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_adam_fused.json > $OUT/bench_adam.log 2>&1 || true
+  timeout -k 10 300 python bench.py --full --adam fused --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs --json-out $OUT/bench_adam_fused.json > $OUT/bench_adam.log 2>&1 || true
   timeout -k 10 200 python scripts/dev/knn_bench.py > $OUT/knn_bench.json 2>&1 || true
   timeout -k 10 200 python scripts/dev/det_bench.py > $OUT/det_bench.json 2>&1 || true
   GS2D_LIB_PATH=$PWD/scripts/dev/variants/libprof.so timeout -k 10 200 python scripts/dev/wave_profile.py > $OUT/wave_profile.txt 2>&1 || true
@@ -42,8 +42,8 @@ elif [ "$PART" = "2" ]; then
   tail -1 $OUT/knn_bench.json; tail -1 $OUT/det_bench.json; tail -1 $OUT/cull_tightness.json
 fi
 if [ "$PART" = "3" ]; then
-  timeout -k 10 400 python bench.py --json-out $OUT/bench_final.json > $OUT/bench_final.log 2>&1 || true
+  timeout -k 10 400 python bench.py --full --json-out $OUT/bench_final.json > $OUT/bench_final.log 2>&1 || true
   tail -c 300 $OUT/bench_final.log
-  timeout -k 10 300 python bench.py --gpus 2 --backend gloo --share-device --steps 5 --warmup 2 --no-cpu-baseline --json-out $OUT/bench_rehearsal_2ranks_gloo_one_gpu.json > $OUT/bench_rehearsal.log 2>&1 || true
+  timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --share-device --steps 5 --warmup 2 --no-cpu-baseline --json-out $OUT/bench_rehearsal_2ranks_gloo_one_gpu.json > $OUT/bench_rehearsal.log 2>&1 || true
   tail -c 600 $OUT/bench_rehearsal.log
 fi

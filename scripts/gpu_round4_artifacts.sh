@@ -11,7 +11,7 @@ PART=${2:-prof:op}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="--no-cpu-baseline --no-extra-legs"
+B="--full --no-cpu-baseline --no-extra-legs"
 prof() {  # prof <workload>
   local w=$1; local D=$GRAFT_REPO_ROOT/$OUT/prof_$w; local WL=""
   [ "$w" != "op" ] && WL="--workload $w"
@@ -49,8 +49,8 @@ misc)
   timeout -k 10 300 python scripts/dev/cull_tightness.py > $OUT/cull_tightness.json 2>&1 || true
   tail -1 $OUT/knn_bench.json; tail -1 $OUT/det_bench.json; tail -1 $OUT/cull_tightness.json; cat $OUT/timeline_k1.txt ;;
 final)
-  timeout -k 10 400 python bench.py --json-out $OUT/bench_final.json > $OUT/bench_final.log 2>&1 || true
+  timeout -k 10 400 python bench.py --full --json-out $OUT/bench_final.json > $OUT/bench_final.log 2>&1 || true
   tail -c 300 $OUT/bench_final.log
-  timeout -k 10 300 python bench.py --gpus 2 --backend gloo --share-device --steps 5 --warmup 2 --no-cpu-baseline --json-out $OUT/bench_rehearsal_2ranks_gloo_one_gpu.json > $OUT/bench_rehearsal.log 2>&1 || true
+  timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --share-device --steps 5 --warmup 2 --no-cpu-baseline --json-out $OUT/bench_rehearsal_2ranks_gloo_one_gpu.json > $OUT/bench_rehearsal.log 2>&1 || true
   tail -c 400 $OUT/bench_rehearsal.log ;;
 esac
