@@ -918,10 +918,11 @@ int gs2d_backward_staged(int stages, int g_begin, int g_end, int P, int D, int M
         }
     }
     const bool det = known ? fr.det != 0 : false;
-    // Pose-only fast path (tracking with every Gaussian parameter detached): both stages in this call, no per-Gaussian output
-    // of any kind, non-deterministic mode.  The blend stage then accumulates only the three dL_dT components dL/dmean needs, in
-    // a dense layout over the head of the gradient records, and a 40-B-per-Gaussian kernel reduces the pose gradient from them.
-    const bool pose_fast = (stages & 3) == 3 && pose_Rt != nullptr && dL_dmean3D == nullptr && dL_dtransMat == nullptr &&
+    // Pose-only fast path (tracking with every Gaussian parameter detached): both stages in this call on all of [0, P), no
+    // per-Gaussian output of any kind, non-deterministic mode.  The blend stage then accumulates only the three dL_dT components
+    // dL/dmean needs, in a dense layout over the head of the gradient records, and a 40-B-per-Gaussian kernel reduces the pose
+    // gradient from them -- over all P Gaussians, and later PREPROCESS calls could not read the dense layout as records.
+    const bool pose_fast = (stages & 3) == 3 && g_begin == 0 && g_end == P && pose_Rt != nullptr && dL_dmean3D == nullptr && dL_dtransMat == nullptr &&
                            dL_dnormal == nullptr && dL_dsh == nullptr && shs == nullptr && scales != nullptr &&
                            rotations != nullptr && !det && !live_det;
     if (dL_dpose != nullptr && (stages & 1) != 0 && (R <= 0 || det))

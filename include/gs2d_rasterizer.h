@@ -163,7 +163,8 @@ int gs2d_backward_posed(
  * outputs (same full-size output pointers; only rows of that range are written).  A caller that shards keyframes over GPUs
  * (gaus_slam_amd/ba_shard.py) runs BLEND once and PREPROCESS chunk by chunk, starting the gradient all-reduce of a chunk
  * while the next chunk is still being computed.  gs2d_backward_posed == stages 3 on [0, P).  dL_dpose accumulates over the
- * PREPROCESS calls and is cleared by the BLEND call.
+ * PREPROCESS calls and is cleared by the BLEND call.  A pose-only call (all six per-Gaussian outputs NULL) may be split the
+ * same way; its faster pose-only path is taken only by a one-shot call, stages 3 on [0, P) outside the deterministic mode.
  */
 #define GS2D_BWD_BLEND 1
 #define GS2D_BWD_PREPROCESS 2

@@ -137,6 +137,24 @@ def test_staged_backward_rejects_bad_stage_masks(hiplib):
         assert b"stages" in hiplib.gs2d_last_error() or b"GS2D_BWD_POSE_4X4" in hiplib.gs2d_last_error()
 
 
+def test_staged_backward_rejects_bad_gaussian_ranges(hiplib):
+    """With P > 0, a PREPROCESS range outside [0, P) or with g_begin > g_end is an error with a message, raised before any
+    buffer or the GPU is touched: the forward-state buffers are NULL here, and the nine gradient outputs point at a host
+    word the library must never dereference."""
+    argt = hiplib.gs2d_backward_staged.argtypes
+    assert len(argt) == 43
+    P = 1000
+    never = C.c_float(0.0)
+    outs = range(28, 37)  # dL_dmean2D .. dL_drot
+    for stages in (1, 2, 3):
+        for g0, g1 in ((-1, P), (0, P + 1), (10, 9), (P, P - 1), (-5, -1)):
+            args = [stages, g0, g1, P] + [None if t in (C.c_void_p, C.c_char_p) else 0 for t in argt[4:]]
+            for i in outs:
+                args[i] = C.addressof(never)
+            assert hiplib.gs2d_backward_staged(*args) < 0, (stages, g0, g1)
+            assert b"bad Gaussian range" in hiplib.gs2d_last_error(), (stages, g0, g1)
+
+
 def test_deterministic_backward_refuses_chunks_without_a_forward_record(hiplib):
     """The deterministic backward appends 320 B x R of partial records to the binning chunk, so it only ever runs on a chunk
     whose forward this library recorded (mode, R, size).  With the flag on, a backward on unknown chunks must fail with a
