@@ -345,11 +345,15 @@ static inline float relm(float a, float b) /* relative distance of a from thresh
  * exp_std = (D2 - 2 Dp m) / (1 - T) + m^2 is a variance formed by cancellation and conf = exp(-e^2 / (4 exp_std)) divides by
  * it; where the splats in front of a pixel lie at nearly one depth, exp_std is rounding noise of terms of size m^2 and conf
  * -- hence the depth channels -- moves by far more than the arithmetic that produced the noise.  The plane holds
- *   sum_k  w_k |e_k| conf_k (e_k^2 / (4 s_k)) (c_k / s_k),   c_k = m^2 + (|D2| + 2 |Dp m|) / (1 - T),  s_k = exp_std (clamped),
- * i.e. d(depth) / d(relative perturbation of the cancelling terms): multiplied by the relative rounding of float32 sums
- * (1e-6, a dozen ulps) it bounds what two correct float32 evaluations of the reference's formulas may differ by at that pixel.
- * 0 without use_sa.
+ *   sum_k  w_k |e_k| max(|conf(s_k + d_k) - conf_k|, |conf_k - conf(max(s_k - d_k, 1e-7))|) / SA_REL,
+ *   c_k = m^2 + (|D2| + 2 |Dp m|) / (1 - T),  s_k = exp_std (clamped),  d_k = SA_REL c_k,  SA_REL = 2^-22 (four ulps),
+ * i.e. how far the depth moves when the cancelling terms move by SA_REL (relative), per unit of SA_REL: multiplied by SA_REL
+ * (tests/util.py SA_EPS) it bounds what two correct float32 evaluations of the reference's formulas may differ by at that
+ * pixel.  A finite difference, not the derivative conf_k (e_k^2 / (4 s_k)) (c_k / s_k) it equals where d_k << s_k: on planar
+ * scenes (walls, floors) d_k is many times s_k -- exp_std is below one ulp of m^2 -- and the derivative at the float32 point
+ * understated the oracle's own distance from the float64 evaluation (orc_blend_fwd_f64) up to 1e24-fold.  0 without use_sa.
  */
+#define SA_REL 2.384185791015625e-07f /* 2^-22 */
 void orc_blend_fwd(int W, int H, const uint32_t* ranges, const uint32_t* point_list,
                    const float* means2D, const float* features, const float* transMats,
                    const float* normal_opacity, const float* bg, int use_sa,
@@ -423,7 +427,9 @@ void orc_blend_fwd(int W, int H, const uint32_t* ranges, const uint32_t* point_l
                             const float conf = expf(-(e * e) * (1.0f / (4 * exp_std)));
                             if (stab) {
                                 const float cmag = exp_depth * exp_depth + (fabsf(D2) + 2.0f * fabsf(Dp * exp_depth)) / (1 - T);
-                                sa_amp += w * fabsf(e) * conf * ((e * e) / (4 * exp_std)) * (cmag / exp_std);
+                                const float s_hi = exp_std + SA_REL * cmag, s_lo = fmaxf(exp_std - SA_REL * cmag, 1e-7f);
+                                const float c_hi = expf(-(e * e) * (1.0f / (4 * s_hi))), c_lo = expf(-(e * e) * (1.0f / (4 * s_lo)));
+                                sa_amp += w * fabsf(e) * fmaxf(fabsf(c_hi - conf), fabsf(conf - c_lo)) / SA_REL;
                             }
                             depth = fmaf(conf, depth, (1 - conf) * exp_depth);
                         }
@@ -472,7 +478,8 @@ void orc_blend_fwd(int W, int H, const uint32_t* ranges, const uint32_t* point_l
  * is numbered in the order it is met; bit i of `flipmask` inverts decision i.  flipmask = 0 reproduces orc_blend_fwd
  * for that pixel exactly.  A 1-ulp difference in expf / rcp can legitimately flip such a decision, so a GPU value at a
  * knife-edge pixel has to equal ONE of these variants.  Returns the number of knife-edge decisions met.
- * out[13] = color[3], others[7], last_contributor, median_contributor, final_T.
+ * out[14] = color[3], others[7], last_contributor, median_contributor, final_T, sa_amp (the conditioning plane of
+ * orc_blend_fwd for this outcome: a flipped decision may change the splats use_sa re-weights).
  */
 int orc_blend_fwd_pixel(int W, int H, int px, int py, const uint32_t* ranges, const uint32_t* point_list,
                         const float* means2D, const float* features, const float* transMats,
@@ -489,6 +496,7 @@ int orc_blend_fwd_pixel(int W, int H, int px, int py, const uint32_t* ranges, co
     float median_contributor = -1;
     uint32_t contributor = 0, last_contributor = 0;
     int nk = 0;
+    float sa_amp = 0.f;
 #define KNIFE_DECIDE(cond, a, b)                                                           \
     ({ int d_ = (cond);                                                                     \
        if (relm((a), (b)) <= knife) { if (nk < 32 && ((flipmask >> nk) & 1u)) d_ = !d_; nk++; } \
@@ -531,6 +539,10 @@ int orc_blend_fwd_pixel(int W, int H, int px, int py, const uint32_t* ranges, co
                 exp_std = fmax_c(exp_std, 1e-7f);
                 const float e = exp_depth - depth;
                 const float conf = expf(-(e * e) * (1.0f / (4 * exp_std)));
+                const float cmag = exp_depth * exp_depth + (fabsf(D2) + 2.0f * fabsf(Dp * exp_depth)) / (1 - T);
+                const float s_hi = exp_std + SA_REL * cmag, s_lo = fmaxf(exp_std - SA_REL * cmag, 1e-7f);
+                const float c_hi = expf(-(e * e) * (1.0f / (4 * s_hi))), c_lo = expf(-(e * e) * (1.0f / (4 * s_lo)));
+                sa_amp += w * fabsf(e) * fmaxf(fabsf(c_hi - conf), fabsf(conf - c_lo)) / SA_REL;
                 depth = fmaf(conf, depth, (1 - conf) * exp_depth);
             }
             Dp = fmaf(depth, w, Dp);
@@ -558,6 +570,7 @@ int orc_blend_fwd_pixel(int W, int H, int px, int py, const uint32_t* ranges, co
     out[10] = (float)last_contributor;
     out[11] = median_contributor < 0 ? 0.f : median_contributor;
     out[12] = T;
+    out[13] = sa_amp;
     return nk;
 }
 

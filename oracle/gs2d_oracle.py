@@ -5,6 +5,11 @@ bench.py's cpu_baseline leg.  The shipped package (gaus_slam_amd/) never
 imports this module.  Parity status: "parity unpinned" against the reference
 binary (see the header of gs2d_oracle.c and DESIGN.md).
 
+forward_f64 / backward_f64 (oracle/gs2d_oracle_f64.c) evaluate the forward
+blend and the backward in float64 on the float32 paths' inputs and discrete
+decisions: the yardstick that tells a float32 path's rounding error from a
+formula difference (tests/util.py check_allmap, the backward rounding tests).
+
 The call structure mirrors the reference stage driver
 RAST/cuda_rasterizer/rasterizer_impl.cu:201-350 (forward) and :354-460
 (backward), and the tensor conventions of RAST/rasterize_points.cu:39-239.
@@ -180,19 +185,20 @@ def reblend(st, ranges, point_list, want_stability=True):
 def pixel_variants(st, px, py, knife, max_decisions=6):
     """All outcomes of the forward blend at pixel (px, py) when the decisions within `knife` (relative) of their threshold
     are flipped in every combination (orc_blend_fwd_pixel).  Returns (n_decisions, list of dicts color[3], others[7],
-    last_contributor, median_contributor, final_T); n_decisions > max_decisions returns only the unflipped variant."""
+    last_contributor, median_contributor, final_T, sa_amp -- that outcome's use_sa conditioning, the plane forward() returns
+    as st["sa_amp"]); n_decisions > max_decisions returns only the unflipped variant."""
     L = lib()
     L.orc_blend_fwd_pixel.restype = C.c_int
     features = st["colors_precomp"] if st["colors_precomp"] is not None else st["rgb"]
     tm = st["transMat_precomp"] if st["transMat_precomp"] is not None else st["transMats"]
 
     def one(mask):
-        out = np.zeros(13, np.float32)
+        out = np.zeros(14, np.float32)
         nk = L.orc_blend_fwd_pixel(C.c_int(st["W"]), C.c_int(st["H"]), C.c_int(int(px)), C.c_int(int(py)), _p(st["ranges"]),
                                    _p(st["point_list"]), _p(st["means2D"]), _p(features), _p(tm), _p(st["normal_opacity"]),
                                    _p(st["bg"]), C.c_int(int(st["use_sa"])), C.c_float(knife), C.c_uint32(mask), _p(out))
         return nk, dict(color=out[0:3].copy(), others=out[3:10].copy(), last_contributor=int(out[10]),
-                        median_contributor=int(out[11]), final_T=float(out[12]))
+                        median_contributor=int(out[11]), final_T=float(out[12]), sa_amp=float(out[13]))
 
     nk, base = one(0)
     base["mask"] = 0
@@ -271,6 +277,31 @@ def backward(st, dL_dcolor, dL_dallmap, pixel_overrides=None, knife=0.0, forms=N
                          _p(g["dL_dmeans2D"]), _p(g["dL_dmeans3D"]), _p(g["dL_dscales"]),
                          _p(g["dL_drotations"]))
     return g
+
+
+def forward_f64(st):
+    """The forward blend of a forward() state evaluated in FLOAT64 on the float32 paths' inputs and discrete decisions
+    (oracle/gs2d_oracle_f64.c orc_blend_fwd_f64): the same lists, means2D, features (colours or st["rgb"] from SH),
+    transMats (or transMat_precomp), normal_opacity and bg as orc_blend_fwd; the decisions from a float32 shadow of it.  The
+    yardstick that tells a float32 forward's rounding error from a formula difference -- use_sa's depth channels above all.
+    Returns float64 color [3,H,W], allmap [7,H,W], final_T [H,W], M1 / M2 [H,W], sa_mag [H,W] (channel 6's cancellation
+    magnitude m^2 (1-T) + 2 |m Dp| + |D2| under use_sa, 0 otherwise) and the shadow's n_contrib [2*HW] (uint32)."""
+    L = lib()
+    W, H = st["W"], st["H"]
+    HW = H * W
+    color = np.zeros((3, H, W), np.float64)
+    allmap = np.zeros((7, H, W), np.float64)
+    final_T = np.zeros(3 * HW, np.float64)
+    n_contrib = np.zeros(2 * HW, np.uint32)
+    sa_mag = np.zeros(HW, np.float64)
+    if st["P"] > 0:
+        features = st["colors_precomp"] if st["colors_precomp"] is not None else st["rgb"]
+        tm = st["transMat_precomp"] if st["transMat_precomp"] is not None else st["transMats"]
+        L.orc_blend_fwd_f64(C.c_int(W), C.c_int(H), _p(st["ranges"]), _p(st["point_list"]), _p(st["means2D"]), _p(features),
+                            _p(tm), _p(st["normal_opacity"]), _p(st["bg"]), C.c_int(int(st["use_sa"])),
+                            _p(color), _p(allmap), _p(final_T), _p(n_contrib), _p(sa_mag))
+    return dict(color=color, allmap=allmap, final_T=final_T[:HW].reshape(H, W), M1=final_T[HW:2 * HW].reshape(H, W),
+                M2=final_T[2 * HW:].reshape(H, W), sa_mag=sa_mag.reshape(H, W), n_contrib=n_contrib)
 
 
 def backward_f64(st, dL_dcolor, dL_dallmap):

@@ -1,5 +1,6 @@
 /*
- * gs2d_oracle_f64.c -- CPU ORACLE, float64 evaluation of the backward (test infrastructure, NOT product code).
+ * gs2d_oracle_f64.c -- CPU ORACLE, float64 evaluation of the forward blend and of the backward (test infrastructure, NOT
+ * product code).
  *
  * Purpose: a yardstick for float32 rounding.  The float32 oracle (gs2d_oracle.c) and the HIP kernels evaluate the same
  * backward (RAST/cuda_rasterizer/backward.cu:143-664) in two different float32 operation orders; which of the two is closer
@@ -12,6 +13,12 @@
  *     (pixels whose decisions are within rounding of a threshold are kept out of such comparisons by the tests);
  *   - all continuous arithmetic is double, exp() is libm's double exp.
  * err(float32 path, this) is then that path's rounding error, per entry.
+ * orc_blend_fwd_f64 does the same for the forward blend (forward.cu:258-467): its float32 shadow repeats orc_blend_fwd's
+ * arithmetic for the decisions (p2 == 0, the near plane, power > 0, alpha < 1/255, the 0.99 clamp, test_T < 1e-4, T > 0.5 for
+ * the median, ray-splat vs low-pass), everything continuous -- alpha, weights, C, N, Dp, D2, M1, M2, distortion and use_sa's
+ * depth re-weighting with its 1e-7 clamp -- is double.  use_sa's conf divides by a variance formed by cancellation
+ * (forward.cu:405-416): on planar scenes two float32 evaluations differ there by far more than their rounding, and only a
+ * float64 evaluation tells which of them is the more accurate.
  *
  * PARITY STATUS: as gs2d_oracle.c -- "parity unpinned" against the reference binary.
  * Build: part of libgs2d_oracle.so (oracle/Makefile).
@@ -26,6 +33,123 @@
 #define FAR_N 100.0f
 #define FILTER_INV_SQ 100.0f
 #define ACC_STRIDE 20 /* layout of orc_blend_bwd: [0..2] colour, [3..5] normal, [6..14] dT, [15,16] mean2D, [17] opacity */
+
+/*
+ * forward.cu:258-467 in double on float32 decisions.  Outputs (double): out_color [3,H,W] (background included),
+ * out_others [7,H,W] (the allmap), final_T [3,HW] (T, M1, M2); n_contrib [2,HW] (last / median contributor) is the float32
+ * shadow's, i.e. orc_blend_fwd's own counts.  sa_mag [HW] (optional) receives the cancellation magnitude of channel 6 under
+ * use_sa, m^2 (1 - T) + 2 |m Dp| + |D2| (0 without use_sa): channel 6 is that much rounded float32 terms cancelling to a
+ * value that may be 1e-6 of it, so its float32 error is measured relative to sa_mag.
+ */
+void orc_blend_fwd_f64(int W, int H, const uint32_t* ranges, const uint32_t* point_list,
+                       const float* means2D, const float* features, const float* transMats,
+                       const float* normal_opacity, const float* bg, int use_sa,
+                       double* out_color, double* out_others, double* final_T, uint32_t* n_contrib, double* sa_mag)
+{
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    const size_t HW = (size_t)H * W;
+    const double c1 = (double)FAR_N / ((double)FAR_N - (double)NEAR_N);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int tile = 0; tile < gx * gy; tile++) {
+        const int tx = tile % gx, ty = tile / gx;
+        const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
+        for (int ly = 0; ly < TILE; ly++)
+            for (int lx = 0; lx < TILE; lx++) {
+                const int px = tx * TILE + lx, py = ty * TILE + ly;
+                if (px >= W || py >= H) continue;
+                const size_t pix = (size_t)W * py + px;
+                const float pxf = (float)px, pyf = (float)py;
+                const double pxd = px, pyd = py;
+                float Tf = 1.0f;   /* float32 shadow of the transmittance: decides test_T < 1e-4 and T > 0.5 */
+                int any = 0;       /* orc_blend_fwd's Dp > 0: Dp is a sum of w * depth with w >= 4e-7, depth >= 0.2 */
+                double T = 1.0, Cc[3] = {0, 0, 0}, N[3] = {0, 0, 0};
+                double Dp = 0, M1 = 0, M2 = 0, D2 = 0, distortion = 0, median_depth = 0;
+                float median_contributor = -1;
+                uint32_t contributor = 0, last_contributor = 0;
+                for (uint32_t it = r0; it < r1; it++) {
+                    contributor++;
+                    const uint32_t g = point_list[it];
+                    const float* Tm = transMats + 9 * (size_t)g;
+                    /* ---- float32 shadow: the arithmetic of orc_blend_fwd, for the decisions only */
+                    const float kf[3] = {fmaf(pxf, Tm[6], -Tm[0]), fmaf(pxf, Tm[7], -Tm[1]), fmaf(pxf, Tm[8], -Tm[2])};
+                    const float lf[3] = {fmaf(pyf, Tm[6], -Tm[3]), fmaf(pyf, Tm[7], -Tm[4]), fmaf(pyf, Tm[8], -Tm[5])};
+                    const float p0f = fmaf(kf[1], lf[2], -(kf[2] * lf[1]));
+                    const float p1f = fmaf(kf[2], lf[0], -(kf[0] * lf[2]));
+                    const float p2f = fmaf(kf[0], lf[1], -(kf[1] * lf[0]));
+                    if (p2f == 0.0f) continue;
+                    const float ipf = 1.0f / p2f;
+                    const float s0f = p0f * ipf, s1f = p1f * ipf;
+                    const float rho3df = fmaf(s0f, s0f, s1f * s1f);
+                    const float d0f = means2D[2 * (size_t)g] - pxf, d1f = means2D[2 * (size_t)g + 1] - pyf;
+                    const float rho2df = FILTER_INV_SQ * fmaf(d0f, d0f, d1f * d1f);
+                    const int ray = rho3df <= rho2df;
+                    const float rhof = fminf(rho3df, rho2df);
+                    const float depthf = ray ? fmaf(s0f, Tm[6], fmaf(s1f, Tm[7], Tm[8])) : Tm[8];
+                    if (depthf < NEAR_N) continue;
+                    const float* no = normal_opacity + 4 * (size_t)g;
+                    const float powerf = -0.5f * rhof;
+                    if (powerf > 0.0f) continue;
+                    const float Gf = expf(powerf);
+                    const int clamped = !(no[3] * Gf < 0.99f); /* fminf(0.99f, x): the clamp wins unless x < 0.99 */
+                    const float alphaf = fminf(0.99f, no[3] * Gf);
+                    if (alphaf < 1.0f / 255.0f) continue;
+                    const float test_Tf = Tf * (1 - alphaf);
+                    if (test_Tf < 0.0001f) break; /* done = true */
+                    const int upd_median = Tf > 0.5f;
+                    const int had = any;
+                    Tf = test_Tf;
+                    any = 1;
+                    /* ---- double evaluation on those decisions */
+                    const double Tu[3] = {Tm[0], Tm[1], Tm[2]}, Tv[3] = {Tm[3], Tm[4], Tm[5]}, Tw[3] = {Tm[6], Tm[7], Tm[8]};
+                    const double k[3] = {pxd * Tw[0] - Tu[0], pxd * Tw[1] - Tu[1], pxd * Tw[2] - Tu[2]};
+                    const double l[3] = {pyd * Tw[0] - Tv[0], pyd * Tw[1] - Tv[1], pyd * Tw[2] - Tv[2]};
+                    const double p0 = k[1] * l[2] - k[2] * l[1], p1 = k[2] * l[0] - k[0] * l[2], p2 = k[0] * l[1] - k[1] * l[0];
+                    const double s0 = p0 / p2, s1 = p1 / p2;
+                    const double d0 = (double)means2D[2 * (size_t)g] - pxd, d1 = (double)means2D[2 * (size_t)g + 1] - pyd;
+                    const double rho = ray ? s0 * s0 + s1 * s1 : (double)FILTER_INV_SQ * (d0 * d0 + d1 * d1);
+                    double depth = ray ? s0 * Tw[0] + s1 * Tw[1] + Tw[2] : Tw[2];
+                    const double alpha = clamped ? (double)0.99f : (double)no[3] * exp(-0.5 * rho);
+                    const double w = alpha * T;
+                    if (upd_median) { median_depth = depth; median_contributor = (float)contributor; }
+                    if (use_sa) { /* forward.cu:405-416 */
+                        if (had) {
+                            const double m = median_depth;
+                            const double exp_std = fmax((D2 - 2.0 * Dp * m) / (1.0 - T) + m * m, (double)1e-7f);
+                            const double e = m - depth;
+                            const double conf = exp(-(e * e) / (4.0 * exp_std));
+                            depth = conf * depth + (1.0 - conf) * m;
+                        }
+                        Dp += depth * w;
+                        D2 += depth * depth * w;
+                    } else { /* forward.cu:417-423 */
+                        const double A = 1.0 - T;
+                        const double m = c1 * (1.0 - (double)NEAR_N / depth);
+                        distortion += (m * m * A - 2.0 * m * M1 + M2) * w;
+                        Dp += depth * w;
+                        M1 += m * w;
+                        M2 += m * m * w;
+                    }
+                    for (int ch = 0; ch < 3; ch++) N[ch] += (double)no[ch] * w;
+                    for (int ch = 0; ch < 3; ch++) Cc[ch] += (double)features[3 * (size_t)g + ch] * w;
+                    T *= 1.0 - alpha;
+                    last_contributor = contributor;
+                }
+                final_T[pix] = T;
+                final_T[pix + HW] = M1;
+                final_T[pix + 2 * HW] = M2;
+                n_contrib[pix] = last_contributor;
+                n_contrib[pix + HW] = median_contributor < 0 ? 0u : (uint32_t)median_contributor;
+                for (int ch = 0; ch < 3; ch++) out_color[ch * HW + pix] = Cc[ch] + T * (double)bg[ch];
+                out_others[pix + 0 * HW] = Dp;
+                out_others[pix + 1 * HW] = 1.0 - T;
+                for (int ch = 0; ch < 3; ch++) out_others[pix + (2 + ch) * HW] = N[ch];
+                out_others[pix + 5 * HW] = median_depth;
+                const double m = median_depth;
+                out_others[pix + 6 * HW] = use_sa ? m * m * (1.0 - T) - 2.0 * m * Dp + D2 : distortion;
+                if (sa_mag) sa_mag[pix] = use_sa ? m * m * (1.0 - T) + 2.0 * fabs(m * Dp) + fabs(D2) : 0.0;
+            }
+    }
+}
 
 /*
  * backward.cu:143-463 in double on float32 decisions.  Outputs (double): dL_dtransMat [P,9], dL_dmean2D [P,3] (z = 0),

@@ -79,7 +79,7 @@ def test_footprint_lists_change_nothing(oracle, regime, use_sa, P, W, H):
     np.testing.assert_array_equal(ht["last_contributor"][stable], ot["n_contrib"][:HW].reshape(H, W)[stable])
     np.testing.assert_array_equal(ht["median_contributor"][stable], ot["n_contrib"][HW:].reshape(H, W)[stable])
     assert np.abs(ht["color"] - ot["color"])[:, stable].max() <= IMG_TOL
-    assert (util.allmap_dev(ht, ot, stable) <= IMG_TOL).all()
+    util.check_allmap(ht, ot, stable, tol=IMG_TOL)
     util.check_knife_pixels(oracle, ot, ht, stable, IMG_TOL, KNIFE)
     gh = util.hip_backward(ht, dc, da)
     for k in GRADS:

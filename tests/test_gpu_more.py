@@ -86,7 +86,7 @@ def test_debug_flag_and_scale_modifier(oracle):
     h = util.hip_forward(sc, scale_modifier=1.7, debug=True)
     np.testing.assert_array_equal(h["point_list"], o["point_list"])
     stable = (o["stability"] > KNIFE).reshape(80, 96)
-    assert util.allmap_dev(h, o, stable).max() <= IMG_TOL
+    util.check_allmap(h, o, stable, tol=IMG_TOL)
 
 
 def test_backward_with_a_scale_modifier(oracle):
@@ -164,7 +164,7 @@ def test_full_bench_size_500k(oracle, regime):
     HW = H * W
     np.testing.assert_array_equal(h["last_contributor"][stable], o["n_contrib"][:HW].reshape(H, W)[stable])
     assert np.abs(h["color"] - o["color"])[:, stable].max() <= IMG_TOL
-    assert util.allmap_dev(h, o, stable).max() <= IMG_TOL
+    util.check_allmap(h, o, stable, tol=IMG_TOL)
     dc, da = util.make_upstream_grads(W, H)
     dc, da = (dc * W * H).numpy(), (da * W * H).numpy()
     dc[:, ~stable] = 0; da[:, ~stable] = 0
@@ -271,7 +271,7 @@ def test_replica_shaped_1200x680(oracle):
     assert (~stable).mean() < 5e-3
     np.testing.assert_array_equal(h["last_contributor"][stable], o["n_contrib"][:H * W].reshape(H, W)[stable])
     assert np.abs(h["color"] - o["color"])[:, stable].max() <= IMG_TOL
-    assert util.allmap_dev(h, o, stable).max() <= IMG_TOL
+    util.check_allmap(h, o, stable, tol=IMG_TOL)
     dc, da = util.make_upstream_grads(W, H, channels=(0, 1))  # tracking loss touches colour, depth, alpha
     dc, da = (dc * W * H).numpy(), (da * W * H).numpy()
     dc[:, ~stable] = 0; da[:, ~stable] = 0
@@ -296,7 +296,7 @@ def test_scannetpp_shaped_1168x876_2M(oracle):
     stable = (o["stability"] > KNIFE).reshape(H, W)
     assert (~stable).mean() < 5e-3
     assert np.abs(h["color"] - o["color"])[:, stable].max() <= IMG_TOL
-    assert util.allmap_dev(h, o, stable).max() <= IMG_TOL
+    util.check_allmap(h, o, stable, tol=IMG_TOL)
     dc, da = util.make_upstream_grads(W, H, channels=(0, 1, 6))
     dc, da = (dc * W * H).numpy(), (da * W * H).numpy()
     dc[:, ~stable] = 0; da[:, ~stable] = 0

@@ -187,37 +187,8 @@ def test_backward_parity_includes_knife_edge_pixels_and_mid_magnitude_entries(or
     # (oracle.backward_f64) is the yardstick: the HIP forms (one merged blend recurrence, closed-form opacity-map term,
     # med + conf (d - med)) must not be further from it than twice the float32 oracle's own operation order is.
     dc[:, ~stable] = 0; da[:, ~stable] = 0   # (float64 has no per-pixel override: knife-edge pixels sit this part out)
-    _assert_rounding_no_worse_than_the_oracles(oracle, o, h, dc, da)
+    util._assert_rounding_no_worse_than_the_oracles(oracle, o, h, dc, da)
     oracle.set_threads(1)
-
-
-F64_GRADS = ["dL_dmeans3D", "dL_dcolors", "dL_dopacity", "dL_dtransMat", "dL_dscales", "dL_drotations"]
-
-
-def _assert_rounding_no_worse_than_the_oracles(oracle, o, h, dc, da, gh=None):
-    """err(HIP, float64) <= 2 err(oracle-float32, float64), per tensor, on the mid-magnitude entries (max and rms of the
-    relative error) and in the max norm.  All three backwards start from the SAME per-pixel forward state -- the HIP
-    forward's (T_final, M1, M2, median, std, contributor counts; they differ from the oracle forward's by that pass's own
-    rounding, which is an input perturbation of the backward, not its arithmetic) -- on the oracle's lists and records, which
-    the HIP forward reproduces bit for bit."""
-    H, W = o["H"], o["W"]
-    oh = dict(o)
-    oh["final_T"] = np.concatenate([h["final_T"].ravel(), h["M1"].ravel(), h["M2"].ravel()]).astype(np.float32)
-    oh["n_contrib"] = np.concatenate([h["last_contributor"].ravel(), h["median_contributor"].ravel()]).astype(np.uint32)
-    oh["median_depth"] = np.ascontiguousarray(h["median_depth"].ravel(), np.float32)
-    oh["depth_std"] = np.ascontiguousarray(h["depth_std"].ravel(), np.float32)
-    go = oracle.backward(oh, dc, da)
-    gh = util.hip_backward(h, dc, da) if gh is None else gh
-    g64 = oracle.backward_f64(oh, dc, da)
-    rep = util.rounding_report(gh, go, g64, F64_GRADS)
-    for k, (h_mid, o_mid, h_max, o_max, h_rms, o_rms) in rep.items():
-        assert h_rms <= 2 * o_rms, (k, "mid-magnitude rms", h_rms, o_rms)
-        assert h_max <= 2 * o_max, (k, "max-norm", h_max, o_max)
-        # the MAX over ~1e5-1e6 mid-magnitude entries is an extreme-value statistic: v_rcp_f32 / v_exp_f32 at their 1-ulp error
-        # bounds alone move it by 2-3x in the CPU emulation (profiles/form_costs_r04.txt: rows RCP, EXP2 + RCP), the four
-        # algebraic rewrites of the kernel by nothing
-        assert h_mid <= 5 * o_mid and h_mid <= MID_TOL / 2, (k, "mid-magnitude max", h_mid, o_mid)
-    return rep
 
 
 def _probe_scene(oracle, P, W, H, seed, use_sa, n_probes=1500):
@@ -321,7 +292,7 @@ def test_full_size_default_mode_against_the_oracle(oracle):
     np.testing.assert_array_equal(ht["last_contributor"][stable], ot["n_contrib"][:HW].reshape(H, W)[stable])
     np.testing.assert_array_equal(ht["median_contributor"][stable], ot["n_contrib"][HW:].reshape(H, W)[stable])
     assert np.abs(ht["color"] - ot["color"])[:, stable].max() <= IMG_TOL
-    assert (util.allmap_dev(ht, ot, stable) <= IMG_TOL).all()
+    util.check_allmap(ht, ot, stable, tol=IMG_TOL)
     util.check_knife_pixels(oracle, ot, ht, stable, IMG_TOL, KNIFE)
     dc, da = util.make_upstream_grads(W, H, seed=1, channels=(0, 1, 2, 3, 4, 5, 6))
     dc, da = (dc * W * H).numpy(), (da * W * H).numpy()
@@ -336,7 +307,7 @@ def test_full_size_default_mode_against_the_oracle(oracle):
         assert util.grad_err(gh[k], ref) <= GRAD_TOL, k
         assert util.grad_err_mid(gh[k], ref) <= MID_TOL, (k, util.grad_err_mid(gh[k], ref))
     # whose rounding is the 9e-4 on dL_dmeans3D?  Both float32 paths against the float64 evaluation (see the 320x240 test)
-    _assert_rounding_no_worse_than_the_oracles(oracle, ot, ht, dc, da, gh=gh)
+    util._assert_rounding_no_worse_than_the_oracles(oracle, ot, ht, dc, da, gh=gh)
     oracle.set_threads(1)
 
 

@@ -316,3 +316,187 @@ def test_float64_backward_matches_float64_autograd_where_exact(oracle):
         # (T_final, M1, M2 ...) reaches the backward rounded to float32 and the splat records are float32 -- inputs of the
         # function, not rounding inside it (float32 oracle vs backward_f64 on the SAME inputs: 1.5-2.7e-7)
         assert util.grad_err(g[gk].reshape(a.shape), a) < 1e-5, (k, util.grad_err(g[gk].reshape(a.shape), a))
+
+
+# ---- the float64 forward blend (oracle.forward_f64): the yardstick of util.check_allmap's use_sa depth rules ----------------
+
+def _f64_case(oracle, case):
+    W, H, P = 320, 240, 4000
+    regime = "mapping" if case in ("mapping", "mapping_nosa") else "tracking"
+    sc = util.make_scene(P, W, H, seed=0, regime=regime)
+    kw = dict(use_sa=not case.endswith("nosa"), bg=(0.2, 0.5, 0.1))
+    if case == "sh3":
+        kw.update(shs=np.random.default_rng(1).normal(0, 0.5, (P, 16, 3)).astype(np.float32), sh_degree=3)
+    if case == "transmat":
+        kw.update(transMat_precomp=util.oracle_forward(oracle, sc, use_sa=True)["transMats"].copy())
+    return util.oracle_forward(oracle, sc, **kw), W, H
+
+
+@pytest.mark.parametrize("case", ["tracking", "mapping", "tracking_nosa", "mapping_nosa", "sh3", "transmat"])
+def test_float64_forward_is_the_float32_oracle_up_to_rounding(oracle, case):
+    """forward_f64 walks orc_blend_fwd's decisions (identical contributor counts) and differs from it by float32 rounding only:
+    colour, alpha, normals within 1e-6 (measured <= 2.3e-7); without use_sa the depth within 4e-6 relative and the distortion
+    within 1e-6 (measured 2.0e-6 / 1.3e-7: Dp sums ~100 float32 products); with use_sa the depth and channel 6 within the
+    conditioning allowance of util.allmap_dev plus that rounding (measured <= 0.72 of it on these scenes)."""
+    st, W, H = _f64_case(oracle, case)
+    f = oracle.forward_f64(st)
+    np.testing.assert_array_equal(f["n_contrib"], st["n_contrib"])
+    stable = (st["stability"] > 2e-5).reshape(H, W)
+    HW = H * W
+    assert np.abs(f["final_T"].ravel() - st["final_T"][:HW]).max() <= 1e-6
+    assert np.abs(f["color"] - st["color"]).max() <= 1e-6
+    assert np.abs(f["allmap"][1:5] - st["allmap"][1:5]).max() <= 1e-6
+    assert (np.abs(f["allmap"][5] - st["allmap"][5]) <= 2.0 ** -22 * np.abs(f["allmap"][5])).all()  # one depth, <= 2 ulps
+    d0, d6 = np.abs(f["allmap"][0] - st["allmap"][0]), np.abs(f["allmap"][6] - st["allmap"][6])
+    if st["use_sa"]:
+        allow = st["sa_amp"].reshape(H, W) * util.SA_EPS
+        assert (d0 <= allow + 4e-6 * np.abs(f["allmap"][0]))[stable].all()
+        assert (d6 <= 8 * allow + util.SA_REL6 * f["sa_mag"])[stable].all()
+        assert (f["sa_mag"][stable] > 0).any()
+    else:
+        assert (d0 <= 4e-6 * np.abs(f["allmap"][0])).all() and d6.max() <= 1e-6
+        assert f["sa_mag"].max() == 0
+
+
+@pytest.mark.parametrize("regime", ["tracking", "mapping"])
+def test_float64_forward_matches_float64_pytorch_restatement(oracle, regime):
+    """The formula pin: forward_f64 against oracle/torch_ref.py evaluated in float64 (use_sa off).  What is left between the two
+    is their preprocess inputs -- forward_f64 blends the float32 records of orc_preprocess, torch_ref its own float64 transforms:
+    measured 8.0e-6 on colour, 5.7e-5 on depth (the same as the float32 oracle against torch_ref); limits 2e-5 / 1.5e-4."""
+    from oracle import torch_ref
+    W, H, P = 160, 120, 256
+    sc = util.make_scene(P, W, H, seed=0, regime=regime)
+    cam = sc["cam"]
+    st = util.oracle_forward(oracle, sc, use_sa=False)
+    f = oracle.forward_f64(st)
+    dt = torch.float64
+    with torch.no_grad():
+        r = torch_ref.render(sc["means3D"].to(dt), sc["scales"].to(dt), sc["rotations"].to(dt), sc["opacities"].to(dt),
+                             sc["colors"].to(dt), cam.viewmatrix.to(dt), cam.projmatrix.to(dt), W, H, use_sa=False)
+    np.testing.assert_array_equal(r["n_contrib"].numpy().reshape(-1), f["n_contrib"])
+    assert np.abs(r["color"].numpy() - f["color"]).max() < 2e-5
+    assert np.abs(r["allmap"].numpy() - f["allmap"]).max() < 1.5e-4
+    assert np.abs(r["allmap"][6].numpy() - f["allmap"][6]).max() < 1e-6
+
+
+@pytest.mark.parametrize("rel", [1e-2, 1e-3, 1e-4, 1e-5])
+def test_float64_forward_use_sa_closed_form(oracle, rel):
+    """Two fronto-parallel surfels on one pixel at depths d and d + delta, the front one taking T below 0.5: the back one is
+    re-weighted towards the median d with conf = exp(-delta^2 / (4 max(exp_std, 1e-7))), where exp_std = (D2 - 2 Dp m) / (1 - T)
+    + m^2 cancels to 0 exactly -- use_sa at its worst.  conf, the re-weighted depth, Dp, D2 and channel 6 by hand in double from
+    the state's float32 records; forward_f64 matches to 1e-12 (channel 6: relative to its cancellation magnitude)."""
+    W, H, d = 33, 33, 3.0
+    delta = rel * d
+    sc = _single_surfel_scene(W, H, [d + delta, d], [0.6, 0.75])
+    st = util.oracle_forward(oracle, sc, use_sa=True)
+    f = oracle.forward_f64(st)
+    x, y = 18, 16  # 2 px off the centre: the ray-splat branch for both (rho3d ~ 0.1 << rho2d ~ 400)
+    tile = (y // 16) * ((W + 15) // 16) + x // 16
+    r0, r1 = st["ranges"][tile]
+    ids = [int(g) for g in st["point_list"][r0:r1]]
+    assert len(ids) == 2
+    rec = []
+    for g in ids:  # front to back
+        Tm = st["transMats"][g].astype(np.float64)
+        k, l = x * Tm[6:9] - Tm[0:3], y * Tm[6:9] - Tm[3:6]
+        p = np.cross(k, l)
+        s = p[:2] / p[2]
+        rec.append((s[0] * Tm[6] + s[1] * Tm[7] + Tm[8], float(st["normal_opacity"][g, 3]) * math.exp(-0.5 * (s @ s))))
+    (dA, a1), (dB, a2) = rec
+    assert a1 > 0.5 and abs(dB - dA - delta) < 1e-5 * d
+    m, T = dA, 1.0 - a1                       # the median stays at the front surfel: T < 0.5 when the back one comes
+    Dp, D2 = dA * a1, dA * dA * a1
+    exp_std = max((D2 - 2 * Dp * m) / (1 - T) + m * m, float(np.float32(1e-7)))
+    conf = math.exp(-((m - dB) ** 2) / (4 * exp_std))
+    dB2 = conf * dB + (1 - conf) * m
+    w2 = a2 * T
+    Dp, D2, T = Dp + dB2 * w2, D2 + dB2 * dB2 * w2, T * (1 - a2)
+    ch6 = m * m * (1 - T) - 2 * m * Dp + D2
+    mag = m * m * (1 - T) + 2 * abs(m * Dp) + abs(D2)
+    got = f["allmap"][:, y, x]
+    assert got[0] == pytest.approx(Dp, rel=1e-12) and got[5] == pytest.approx(m, rel=1e-12)
+    assert got[1] == pytest.approx(1 - T, rel=1e-12)
+    assert abs(got[6] - ch6) <= 1e-12 * mag and f["sa_mag"][y, x] == pytest.approx(mag, rel=1e-12)
+    dev = abs(float(st["allmap"][0, y, x]) - Dp)
+    allow = float(st["sa_amp"].reshape(H, W)[y, x]) * util.SA_EPS
+    print(f"delta/d {rel:.0e}: conf {conf:.6f}; float32 oracle depth deviation {dev:.2e}, its allowance SA_EPS x sa_amp "
+          f"{allow:.2e}; channel 6 {ch6:.3e} (float32 {float(st['allmap'][6, y, x]):.3e}, magnitude {mag:.1f})")
+    assert dev <= allow + 1e-6
+
+
+def _planar_sa_scenes():
+    """The 320x240 planar scenes of tests/test_gpu_sa_planar.py (CPU only here)."""
+    from tests.test_gpu_sa_planar import SCENES
+    return {k: v for k, v in SCENES.items() if v[1] == 320}
+
+
+def test_sa_calibration_on_planar_scenes(oracle):
+    """Where the thresholds of util.check_allmap come from: per planar scene, the float32 oracle's distance from forward_f64 on
+    channels 0 and 6 (stable pixels: max, rms, ratio to the allowance SA_EPS x sa_amp), and the float32 torch_ref path's on
+    a 160x120 wall where its structure matches.  The oracle must be inside its own allowance (|o - f64| <= SA_EPS x sa_amp +
+    IMG_TOL; measured ratio to the allowance <= 1.13) and inside SA_REL6 on channel 6 (measured <= 2.96e-7 relative to sa_mag);
+    check_allmap must accept both float32 paths.  (Before sa_amp became a finite difference the oracle's own distance was
+    up to 1e24 times its allowance on these scenes: the derivative at the float32 point of exp_std said nothing there.)"""
+    from oracle import torch_ref
+    for name, (P, W, H, kw) in _planar_sa_scenes().items():
+        sc = util.make_planar_scene(P, W, H, **kw)
+        o = util.oracle_forward(oracle, sc, use_sa=True)
+        f = oracle.forward_f64(o)
+        stable = (o["stability"] > 2e-5).reshape(H, W)
+        allow = o["sa_amp"].reshape(H, W) * util.SA_EPS
+        d0, d6 = np.abs(o["allmap"][0] - f["allmap"][0]), np.abs(o["allmap"][6] - f["allmap"][6])
+        ratio = (d0 / np.maximum(allow, 1e-30))[stable & (allow > util.SA_WELL)]
+        rel6 = (d6 / np.maximum(f["sa_mag"], 1e-30))[stable]
+        print(f"{name}: ch0 |oracle - f64| max {d0[stable].max():.2e} rms {np.sqrt((d0[stable] ** 2).mean()):.2e}, "
+              f"max ratio to the allowance {ratio.max(initial=0):.2f}; ch6 max {d6[stable].max():.2e} rms "
+              f"{np.sqrt((d6[stable] ** 2).mean()):.2e}, max / sa_mag {rel6.max():.2e}")
+        assert (d0 <= allow + 1e-4)[stable].all() and (d6 <= 8 * allow + 1e-4)[stable].all(), name
+        assert rel6.max() <= util.SA_REL6, name
+        util.check_allmap(o, o, stable, orc=oracle, f64=f, label=name)
+    W, H, P = 160, 120, 4000
+    sc = util.make_planar_scene(P, W, H, seed=1, jitter=1e-3)
+    cam = sc["cam"]
+    o = util.oracle_forward(oracle, sc, use_sa=True)
+    with torch.no_grad():
+        r = torch_ref.render(sc["means3D"], sc["scales"], sc["rotations"], sc["opacities"], sc["colors"], cam.viewmatrix,
+                             cam.projmatrix, W, H, use_sa=True)
+    np.testing.assert_array_equal(r["radii"].numpy(), o["radii"])
+    np.testing.assert_array_equal(r["n_contrib"].numpy().reshape(-1), o["n_contrib"])
+    stable = (o["stability"] > 2e-5).reshape(H, W)
+    rep = util.check_allmap(dict(allmap=r["allmap"].numpy()), o, stable, orc=oracle, force_f64=True, label="torch_ref float32")
+    assert rep["n_ill"] > 0.5 * stable.sum()
+
+
+def test_check_allmap_rejects_planted_use_sa_regressions(oracle):
+    """A stand-in "HIP" result made from the float32 oracle's own output on the 1 mm wall, with a regression planted:
+    (a) +3e-4 on channel 0 at the pixels whose allowance exceeds 2 IMG_TOL (there allmap_dev subtracts all of it);
+    (b) channel 6 scaled by 1.5 (on a 1 mm wall channel 6 is ~3e-7, its float32 error ~2e-6 rms: only the signed-mean rule
+        sees it; on a 3 mm wall too);
+    (c) conf forced to 1 -- the depth not re-weighted -- on every fourth pixel (use_sa = False's channel 0 there).
+    Each fails util.check_allmap; the unmodified oracle output passes it.  (a) and (b) pass allmap_dev: the gap this closes."""
+    W, H, P = 320, 240, 20000
+    for jitter, kinds in ((1e-3, "abc"), (3e-3, "b")):
+        sc = util.make_planar_scene(P, W, H, seed=1, jitter=jitter)
+        o = util.oracle_forward(oracle, sc, use_sa=True)
+        f = oracle.forward_f64(o)
+        stable = (o["stability"] > 2e-5).reshape(H, W)
+        allow = o["sa_amp"].reshape(H, W) * util.SA_EPS
+        util.check_allmap(o, o, stable, orc=oracle, f64=f, label=f"unmodified, jitter {jitter:.0e}")
+        for kind in kinds:
+            h = dict(allmap=o["allmap"].copy())
+            if kind == "a":
+                sel = stable & (allow > 2e-4)
+                assert sel.sum() > 1000
+                h["allmap"][0][sel] += 3e-4
+            elif kind == "b":
+                h["allmap"][6] *= 1.5
+            else:
+                raw = util.oracle_forward(oracle, sc, use_sa=False)["allmap"][0]
+                h["allmap"][0].reshape(-1)[::4] = raw.reshape(-1)[::4]
+            old_ok = bool((util.allmap_dev(h, o, stable) <= 1e-4).all())
+            with pytest.raises(AssertionError) as exc:
+                util.check_allmap(h, o, stable, orc=oracle, f64=f, label=f"planted ({kind})")
+            print(f"jitter {jitter:.0e}, planted ({kind}): allmap_dev alone {'ACCEPTS' if old_ok else 'rejects'} it; "
+                  f"check_allmap rejects it: {str(exc.value)[:90]}")
+            if kind in "ab":
+                assert old_ok, kind
