@@ -85,7 +85,7 @@ def lib():
     L.gs2d_slam_loss.restype = i
     L.gs2d_slam_loss.argtypes = [i, i, i, vp, vp, vp, vp, f, f, f, f, f, i, i, f, f, f, vp, vp, vp, vp, vp, vp]
     L.gs2d_adam_step.restype = i
-    L.gs2d_adam_step.argtypes = [i, vp, vp, f, f, f, i, C.c_ulonglong, vp, vp, vp, vp, vp]
+    L.gs2d_adam_step.argtypes = [i, vp, vp, C.c_double, C.c_double, f, i, C.c_ulonglong, vp, vp, vp, vp, vp]
     L.gs2d_set_deterministic.argtypes = [i]
     L.gs2d_get_deterministic.restype = i
     L.gs2d_set_reference_binning.argtypes = [i]

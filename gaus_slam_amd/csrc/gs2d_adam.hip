@@ -60,7 +60,7 @@ adam_kernel(AdamGroups G, size_t n, float one_m_b1, float b2, float one_m_b2, fl
 
 }  // namespace
 
-extern "C" int gs2d_adam_step(int n_groups, const unsigned long long* group_end, const float* group_lr, float beta1, float beta2,
+extern "C" int gs2d_adam_step(int n_groups, const unsigned long long* group_end, const float* group_lr, double beta1, double beta2,
                               float eps, int step, unsigned long long n, float* param, const float* grad, float* exp_avg,
                               float* exp_avg_sq, void* stream)
 {
@@ -69,7 +69,9 @@ extern "C" int gs2d_adam_step(int n_groups, const unsigned long long* group_end,
     if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) return -1;
     AdamGroups G;
     G.n = n_groups;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    // betas in double, as torch holds them: 1 - beta and the bias corrections are formed before any rounding to float32 (with
+    // beta2 = 0.999f, 1 - beta2 would be 1.0000467e-3 instead of torch's 1e-3)
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     unsigned long long prev = 0;
     for (int g = 0; g < GS2D_ADAM_MAX_GROUPS; g++) {
         if (g < n_groups) {
@@ -84,7 +86,7 @@ extern "C" int gs2d_adam_step(int n_groups, const unsigned long long* group_end,
     size_t blocks = (n4 + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, G, (size_t)n, 1.0f - beta1, beta2,
-                       1.0f - beta2, (float)(1.0 / sqrt(bc2)), eps, param, grad, exp_avg, exp_avg_sq);
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, G, (size_t)n, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)(1.0 / sqrt(bc2)), eps, param, grad, exp_avg, exp_avg_sq);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

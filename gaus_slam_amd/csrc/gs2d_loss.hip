@@ -29,8 +29,8 @@ struct PixelTerms {
     float c[3], d, a, dist, gtd;
     bool c_fin[3], d_fin, dist_fin, d_live;  // d_live: depth gradient reaches D/A (not an outlier, finite)
     bool depth_mask, color_mask;
-    float inv_ae;  // 1 / (A + eps)
-    float Draw;
+    float ae;  // A + eps
+    float dq;  // D / (A + eps) before the outlier zeroing
 };
 
 __device__ __forceinline__ PixelTerms pixel_terms(const LossCfg& L, size_t HW, size_t pix, const float* __restrict__ color,
@@ -40,13 +40,16 @@ __device__ __forceinline__ PixelTerms pixel_terms(const LossCfg& L, size_t HW, s
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) t.c[ch] = nan0(color[ch * HW + pix], t.c_fin[ch]);
     const float D = allmap[pix], A = allmap[HW + pix];
-    t.Draw = D;
     float d = D;
     t.d_live = true;
-    t.inv_ae = 1.f;
+    t.ae = 1.f;
+    t.dq = D;
     if (L.use_weight_norm) {  // render/__init__.py:46-49
-        t.inv_ae = 1.0f / (A + L.eps);
-        d = D * t.inv_ae;
+        // the true float32 quotient, as torch forms it: D * (1 / (A + eps)) rounds twice and is one ulp off on ~30 % of
+        // pixels, which flips the outlier bounds, the d > 1e-5 mask and sign(d - gt) of pixels on those edges
+        t.ae = A + L.eps;
+        d = D / t.ae;
+        t.dq = d;
         if (d > L.depth_far || d < L.depth_near) { d = 0.f; t.d_live = false; }
     }
     bool fin;
@@ -145,7 +148,8 @@ loss_grad_kernel(LossCfg L, int HWi, int nparts, const float* __restrict__ color
         float gD = 0.f, gA = 0.f;
         if (dmask && t.d_live) {
             const float gd = gd_scale * sgn(t.d - t.gtd);
-            if (L.use_weight_norm) { gD = gd * t.inv_ae; gA = -gd * t.Draw * t.inv_ae * t.inv_ae; }
+            // torch's div backward: dD = g / (A + eps), dA = -g * ((D / (A + eps)) / (A + eps))
+            if (L.use_weight_norm) { gD = gd / t.ae; gA = -gd * (t.dq / t.ae); }
             else gD = gd;
         }
         dL_dallmap[pix] = gD;

@@ -304,7 +304,7 @@ int gs2d_slam_loss(int mode, int width, int height, const float* color, const fl
  * 1-based step count used for the bias corrections.  No weight decay, no amsgrad.
  */
 #define GS2D_ADAM_MAX_GROUPS 8
-int gs2d_adam_step(int n_groups, const unsigned long long* group_end, const float* group_lr, float beta1, float beta2,
+int gs2d_adam_step(int n_groups, const unsigned long long* group_end, const float* group_lr, double beta1, double beta2,
                    float eps, int step, unsigned long long n, float* param, const float* grad, float* exp_avg,
                    float* exp_avg_sq, void* stream);
 

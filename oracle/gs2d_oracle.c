@@ -1174,6 +1174,139 @@ void orc_dist2_knn3(int N, const float* pts, float* out)
     }
 }
 
+/*
+ * The same function for large clouds (orc_dist2_knn3_fast): exact 3-NN over a k-d tree, equal to orc_dist2_knn3 bit for
+ * bit.  Every candidate's distance is the same float32 expression ((dx*dx + dy*dy) + dz*dz) inserted by the same update3
+ * rule, and the three smallest values of a multiset do not depend on the order they are visited in; a point that is
+ * skipped could not have entered (below).  A tree rather than a uniform grid: depth clouds are surfaces that fill a grid
+ * unevenly, and a cluster with one far point leaves a grid either one cell wide or a hundred thousand cells deep.
+ *
+ * Pruning is conservative under float32 rounding.  A node's box is the tight float32 bound of its points, so every point
+ * p in it satisfies |p_a - q_a| >= gap_a exactly; lb2 = sum gap_a^2 is formed in double (relative error ~1e-16).  The
+ * float32 distance rounds five times (one subtraction per axis, three squares, two sums: all terms non-negative), so it
+ * is at least d^2 * (1 - 5 * 2^-24) - 5 * 2^-150 (the last term covers subnormal results).  A node is skipped only when
+ * lb2 * (1 - 1e-5) - 2^-140 > b2: then every float32 distance in it exceeds b2 and update3 would reject it.  b2 == 0
+ * ends a query early: no distance is below zero.
+ *
+ * Inputs where a tree is not meaningful use the brute force, whose semantics define them: N < 4, any non-finite
+ * coordinate (a non-finite query gives inf, a non-finite neighbour is never taken), and extents whose squared distances
+ * could overflow float32.
+ */
+typedef struct { float lo[3], hi[3], split; int axis, begin, end, left, right; } KdNode;
+enum { KD_LEAF = 8 };
+
+static void kd_select(int* idx, const float* pts, int axis, int lo, int hi, int k)
+{   /* quickselect with a three-way partition: lattices and duplicates (long runs of equal keys) stay linear */
+    while (hi - lo > 1) {
+        const float a = pts[3 * idx[lo] + axis], b = pts[3 * idx[(lo + hi) / 2] + axis], c = pts[3 * idx[hi - 1] + axis];
+        const float pivot = a < b ? (b < c ? b : (a < c ? c : a)) : (a < c ? a : (b < c ? c : b));
+        int lt = lo, i = lo, gt = hi;
+        while (i < gt) {
+            const float v = pts[3 * idx[i] + axis];
+            if (v < pivot) { const int t = idx[lt]; idx[lt++] = idx[i]; idx[i++] = t; }
+            else if (v > pivot) { const int t = idx[--gt]; idx[gt] = idx[i]; idx[i] = t; }
+            else i++;
+        }
+        if (k < lt) hi = lt;
+        else if (k >= gt) lo = gt;
+        else return;
+    }
+}
+
+static int kd_build(KdNode* nodes, int* count, int* idx, const float* pts, int begin, int end)
+{
+    const int n = (*count)++;
+    KdNode* nd = &nodes[n];
+    for (int a = 0; a < 3; a++) { nd->lo[a] = pts[3 * idx[begin] + a]; nd->hi[a] = nd->lo[a]; }
+    for (int k = begin + 1; k < end; k++)
+        for (int a = 0; a < 3; a++) {
+            const float v = pts[3 * idx[k] + a];
+            if (v < nd->lo[a]) nd->lo[a] = v;
+            if (v > nd->hi[a]) nd->hi[a] = v;
+        }
+    nd->begin = begin; nd->end = end; nd->left = nd->right = -1; nd->axis = 0; nd->split = 0.f;
+    if (end - begin <= KD_LEAF) return n;
+    int axis = 0;
+    for (int a = 1; a < 3; a++)
+        if ((double)nd->hi[a] - nd->lo[a] > (double)nd->hi[axis] - nd->lo[axis]) axis = a;
+    const int mid = begin + (end - begin) / 2;
+    kd_select(idx, pts, axis, begin, end, mid);
+    const float split = pts[3 * idx[mid] + axis];
+    const int left = kd_build(nodes, count, idx, pts, begin, mid);
+    const int right = kd_build(nodes, count, idx, pts, mid, end);
+    nd = &nodes[n];
+    nd->axis = axis; nd->split = split; nd->left = left; nd->right = right;
+    return n;
+}
+
+static double kd_lb2(const KdNode* nd, const float* q)
+{
+    double s = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double v = q[a], g = v < nd->lo[a] ? (double)nd->lo[a] - v : (v > nd->hi[a] ? v - (double)nd->hi[a] : 0.0);
+        s += g * g;
+    }
+    return s;
+}
+
+void orc_dist2_knn3_fast(int N, const float* pts, float* out)
+{
+    int finite = N >= 4;
+    double ext2 = 0.0;
+    if (finite) {
+        double lo[3], hi[3];
+        for (int a = 0; a < 3; a++) lo[a] = hi[a] = pts[a];
+        for (int i = 0; i < N && finite; i++)
+            for (int a = 0; a < 3; a++) {
+                const float v = pts[3 * i + a];
+                if (!isfinite(v)) { finite = 0; break; }
+                if (v < lo[a]) lo[a] = v;
+                if (v > hi[a]) hi[a] = v;
+            }
+        for (int a = 0; a < 3; a++) ext2 += (hi[a] - lo[a]) * (hi[a] - lo[a]);
+    }
+    if (!finite || !(ext2 < 1e37)) { orc_dist2_knn3(N, pts, out); return; }
+
+    int* idx = (int*)malloc(sizeof(int) * (size_t)N);
+    /* leaves hold at least KD_LEAF / 2 points: at most 2N / (KD_LEAF / 2) nodes */
+    KdNode* nodes = (KdNode*)malloc(sizeof(KdNode) * ((size_t)4 * N / KD_LEAF + 4));
+    float* sp = (float*)malloc(sizeof(float) * 3 * (size_t)N);
+    for (int i = 0; i < N; i++) idx[i] = i;
+    int count = 0;
+    kd_build(nodes, &count, idx, pts, 0, N);
+    for (int k = 0; k < N; k++) memcpy(sp + 3 * k, pts + 3 * (size_t)idx[k], 3 * sizeof(float));
+
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int k = 0; k < N; k++) {  /* queries in tree order; self is excluded by position */
+        const float* q = sp + 3 * k;
+        const float x = q[0], y = q[1], z = q[2];
+        float b0 = 3.402823466e+38f, b1 = b0, b2 = b0;
+        int stack[128], top = 0;
+        stack[top++] = 0;
+        while (top > 0 && b2 != 0.f) {
+            const KdNode* nd = &nodes[stack[--top]];
+            if (kd_lb2(nd, q) * (1.0 - 1e-5) - 0x1p-140 > (double)b2) continue;
+            if (nd->left < 0) {
+                for (int j = nd->begin; j < nd->end; j++) {
+                    if (j == k) continue;
+                    const float dx = sp[3 * j] - x, dy = sp[3 * j + 1] - y, dz = sp[3 * j + 2] - z;
+                    const float d = (dx * dx + dy * dy) + dz * dz;
+                    if (d < b2) {
+                        if (d < b1) { b2 = b1; if (d < b0) { b1 = b0; b0 = d; } else b1 = d; }
+                        else b2 = d;
+                    }
+                }
+                continue;
+            }
+            const int near_left = q[nd->axis] < nd->split;  /* the far child first on the stack: the near one pops next */
+            stack[top++] = near_left ? nd->right : nd->left;
+            stack[top++] = near_left ? nd->left : nd->right;
+        }
+        out[idx[k]] = ((b0 + b1) + b2) / 3.0f;
+    }
+    free(sp); free(nodes); free(idx);
+}
+
 void orc_set_threads(int n)
 {
 #ifdef _OPENMP

@@ -190,3 +190,69 @@ def test_render_through_leaves_after_prune_and_cat():
     # the fresh leaves alias the buffer Adam just updated: a second render sees the update without re-fetching
     img2, _ = render_and_grads({k: v.detach().requires_grad_(True) for k, v in new.items()})
     assert float((img2 - img1).abs().max()) > 0
+
+
+@pytest.mark.gpu
+def test_fused_adam_at_production_size():
+    """P = 500 003: n = 13 P = 6 500 039 elements, so the 4096-workgroup grid-stride loop runs, 3 elements take the tail and
+    the group boundaries (3P, 4P, 6P, 10P) fall inside float4s.  Six steps against float64 torch.optim.Adam, then three
+    with the step count near 1000 (bias corrections close to 1).  A slice of elements gets gradients <= 1e-19, where g^2 is
+    subnormal or zero in float32: their moments are compared with torch.optim.Adam run in float32, the precision the
+    reference runs at, so a flush-to-zero build flag cannot pass."""
+    from gaus_slam_amd.ba_shard import GradBucket
+    from gaus_slam_amd.optim import FusedGaussianAdam, GaussianSoA
+    P = 500003
+    g = torch.Generator().manual_seed(5)
+    ks = dict(means3D=3, opacities=1, scales=2, rotations=4, colors=3)
+    fields = {n: torch.randn(P, k, generator=g) for n, k in ks.items()}
+    tiny = slice(1000, 5000)  # rows whose gradients are tiny in every field
+    steps = []
+    for s in range(9):
+        gr = {n: torch.randn(P, k, generator=g) * 10.0 ** float(torch.randint(-6, 1, (1,), generator=g)) for n, k in ks.items()}
+        for n, k in ks.items():
+            gr[n][tiny] = torch.randn(4000, k, generator=g) * 10.0 ** -float(torch.randint(19, 26, (1,), generator=g))
+        steps.append(gr)
+    names = dict(means3D="xyz", opacities="opacity", scales="scaling", rotations="rotation", colors="rgb")
+    refs = {}
+    for dt in (torch.float64, torch.float32):
+        ps = {n: torch.nn.Parameter(t.clone().to(dt)) for n, t in fields.items()}
+        refs[dt] = (ps, torch.optim.Adam([{"params": [ps[n]], "lr": LRS[names[n]]} for n in ps], lr=0.0, eps=1e-15))
+    dev = torch.device("cuda")
+    soa = GaussianSoA({n: t.to(dev) for n, t in fields.items()})
+    opt = FusedGaussianAdam(soa, LRS)
+    bucket = GradBucket(P, dev)
+    assert soa.flat.numel() == 6500039
+    for s, gr in enumerate(steps):
+        if s == 6:  # jump the step count to 997
+            opt.step_count = 996
+            for _, topt in refs.values():
+                for st in topt.state.values():
+                    st["step"] = torch.tensor(996.0)
+        for ps, topt in refs.values():
+            for n, p in ps.items():
+                p.grad = gr[n].clone().to(p.dtype)
+            topt.step()
+        bucket.pack({n: t.to(dev) for n, t in gr.items()})
+        opt.step(bucket.flat)
+        if s in (5, 8):
+            for n in ks:
+                got, want = soa.views[n].cpu().double(), refs[torch.float64][0][n].detach()
+                assert (got - want).abs().max() < 2e-6, (s, n)
+    # the tiny-gradient rows against float32 torch: one step rounds m and v at most three times each (torch may contract its
+    # lerp into an FMA), each rounding within 2^-24 of the step's largest term (|g| for m, v + (1 - b2) g^2 for v); v is
+    # subnormal here, where a rounding is absolute (<= 2^-150).  Nine steps, 2x margin.
+    m_all = opt.exp_avg.cpu().split([k * P for k in ks.values()])
+    v_all = opt.exp_avg_sq.cpu().split([k * P for k in ks.values()])
+    ps32, topt32 = refs[torch.float32]
+    n_sub = 0
+    for (n, k), m, v in zip(ks.items(), m_all, v_all):
+        st = topt32.state[ps32[n]]
+        m_ref, v_ref = st["exp_avg"][tiny], st["exp_avg_sq"][tiny]
+        m, v = m.view(P, k)[tiny], v.view(P, k)[tiny]
+        gmax = torch.stack([gr[n][tiny].abs() for gr in steps]).max(0).values
+        assert ((m - m_ref).abs() <= 2 * 9 * 3 * 2.0 ** -24 * gmax).all(), n
+        assert ((v - v_ref).abs() <= 2 * 9 * 3 * (2.0 ** -150 + 2.0 ** -24 * (v_ref + 1e-3 * gmax * gmax))).all(), n
+        n_sub += int(((v_ref > 0) & (v_ref < torch.finfo(torch.float32).tiny)).sum())
+        p32 = ps32[n].detach()[tiny]
+        assert ((soa.views[n].cpu()[tiny] - p32).abs() <= 2 * 9 * 4 * 2.0 ** -24 * p32.abs()).all(), n
+    assert n_sub > 1000  # the subnormal range was exercised

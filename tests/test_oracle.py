@@ -210,6 +210,49 @@ def test_knn_oracle_matches_kdtree(oracle):
     d = oracle.dist2_knn3(pts)
     dd, _ = cKDTree(pts.astype(np.float64)).query(pts.astype(np.float64), k=4)
     np.testing.assert_allclose(d, (dd[:, 1:] ** 2).mean(1), rtol=1e-4)
+    np.testing.assert_allclose(oracle.dist2_knn3_fast(pts), (dd[:, 1:] ** 2).mean(1), rtol=1e-4)
+
+
+@pytest.mark.parametrize("kind", util.KNN_KINDS + ("room", "sinusoid"))
+def test_fast_knn_oracle_equals_brute_force_bit_for_bit(oracle, kind):
+    """orc_dist2_knn3_fast (k-d tree) against orc_dist2_knn3 (O(N^2)) on every distribution tests/test_gpu_knn.py uses, at
+    N <= 20 000: the tree may only skip points that cannot enter the three smallest float32 distances."""
+    if kind in ("room", "sinusoid"):
+        pts = util.depth_cloud(160, 120, scene=kind, seed=1)
+    else:
+        pts = util.knn_cloud(kind, 20000 if kind != "identical" else 3000, seed=1)
+    np.testing.assert_array_equal(oracle.dist2_knn3_fast(pts), oracle.dist2_knn3(pts))
+
+
+@pytest.mark.parametrize("N", [1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097])
+def test_fast_knn_oracle_small_sizes(oracle, N):
+    pts = util.knn_cloud("normal", N, seed=N)
+    np.testing.assert_array_equal(oracle.dist2_knn3_fast(pts), oracle.dist2_knn3(pts))
+
+
+def test_fast_knn_oracle_nonfinite_and_overflowing_inputs(oracle):
+    """Brute-force semantics where a tree is not meaningful: a non-finite query gives inf, a non-finite point is never a
+    neighbour, and squared distances that overflow float32 are never taken."""
+    pts = util.knn_cloud("nonfinite", 3000, seed=2)
+    got = oracle.dist2_knn3_fast(pts)
+    bad = ~np.isfinite(pts).all(1)
+    assert np.isinf(got[bad]).all()
+    np.testing.assert_array_equal(got[~bad], oracle.dist2_knn3(pts[~bad]))
+    huge = util.knn_cloud("normal", 500, seed=3) * np.float32(1e19)
+    np.testing.assert_array_equal(oracle.dist2_knn3_fast(huge), oracle.dist2_knn3(huge))
+
+
+def test_fast_knn_oracle_handles_a_full_depth_cloud(oracle):
+    """A 1200x680 depth image (~734k points) in seconds, and the result agrees with an independent float64 k-d tree."""
+    import time
+    from scipy.spatial import cKDTree
+    pts = util.depth_cloud(1200, 680, scene="room", seed=2)
+    t0 = time.perf_counter()
+    d = oracle.dist2_knn3_fast(pts)
+    assert time.perf_counter() - t0 < 30.0
+    sel = np.random.default_rng(0).choice(len(pts), 5000, replace=False)
+    dd, _ = cKDTree(pts.astype(np.float64)).query(pts[sel].astype(np.float64), k=4)
+    np.testing.assert_allclose(d[sel], (dd[:, 1:] ** 2).mean(1), rtol=1e-4)
 
 
 def test_higher_msb(oracle):

@@ -413,3 +413,189 @@ def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
         sk.bind(("127.0.0.1", 0))
         return sk.getsockname()[1]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Point clouds for simple_knn.distCUDA2 (float32 [N, 3]): the shapes the SLAM loop feeds it and the ones that stress the
+# kernel's Morton boxes (surfaces, ties, degenerate extents, a collapsed curve).
+
+_ROOM_PLANES = (((0.1, -0.05, 1.0), 4.0), ((-1.0, 0.0, 0.15), 1.8), ((1.0, 0.02, 0.1), 2.2), ((0.03, 1.0, 0.05), 1.2))
+
+
+def depth_cloud(W, H, scene="room", seed=0, drop=0.1):
+    """A back-projected depth image, one point per valid pixel (fx = fy = 525 W / 640, principal point at the centre): what
+    scene/Gaussians.py passes to distCUDA2 for a keyframe.  scene "room": three walls and a floor seen from inside, slightly
+    skewed to the camera; "sinusoid": the smooth surface of scripts/dev/knn_bench.py (its pixel scale at 640 wide).  Depth is
+    quantised to 1 mm and about `drop` of the pixels are invalid, with N kept off a multiple of 64."""
+    rng = np.random.default_rng(seed)
+    f = 525.0 * W / 640.0
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    u, v = (xs - (W - 1) / 2.0) / f, (ys - (H - 1) / 2.0) / f  # the ray of a pixel is (u, v, 1): depth = ray length factor
+    if scene == "room":
+        z = np.full((H, W), np.inf)
+        for n, d in _ROOM_PLANES:
+            n = np.asarray(n) / np.linalg.norm(n)
+            nr = n[0] * u + n[1] * v + n[2]
+            with np.errstate(divide="ignore"):
+                t = np.where(nr > 0, d / nr, np.inf)
+            z = np.minimum(z, t)
+    elif scene == "sinusoid":
+        s = 640.0 / W
+        z = 2.0 + 0.5 * np.sin(xs * s / 40.0) * np.cos(ys * s / 55.0) + 0.02 * rng.random((H, W))
+    else:
+        raise ValueError(scene)
+    z = np.round(z * 1000.0) / 1000.0
+    valid = rng.random((H, W)) >= drop
+    if valid.sum() % 64 == 0:
+        valid[np.nonzero(valid)[0][0], np.nonzero(valid)[1][0]] = False
+    pts = np.stack([u * z, v * z, z], -1)[valid]
+    return pts.astype(np.float32)
+
+
+def knn_cloud(kind, N, seed=0):
+    """Synthetic clouds of about N points (exactly N unless the kind fixes its own size):
+    volume       uniform in [0,4] x [0,3] x [0,5] (scripts/dev/knn_bench.py's volume)
+    normal       i.i.d. standard normal
+    plane        uniform on z = 1.5: zero extent on one axis (the kernel's ext == 0 Morton path)
+    lattice      the integer lattice of round(N^(1/3))^3 points, shuffled: equal distances everywhere
+    duplicates   a volume where 30 % of the points are copies of 200 sites
+    identical    N copies of one point
+    cluster_far  a tight normal cluster and one point 1e4 away: the Morton order collapses into a few codes
+    offset_mm    a 1 mm lattice, sparsely filled, offset to (1000, -2000, 500): spacing of ~16 float32 ulps
+    collinear    points on one line in a general direction
+    nonfinite    a normal cloud with NaN, +inf and -inf coordinates in about 2 % of the rows"""
+    rng = np.random.default_rng(seed)
+    if kind == "volume":
+        pts = rng.random((N, 3)) * np.array([4.0, 3.0, 5.0])
+    elif kind == "normal":
+        pts = rng.normal(size=(N, 3))
+    elif kind == "plane":
+        pts = np.concatenate([rng.random((N, 2)) * np.array([3.0, 2.0]), np.full((N, 1), 1.5)], 1)
+    elif kind == "lattice":
+        n = int(round(N ** (1.0 / 3.0)))
+        g = np.stack(np.meshgrid(*(np.arange(n, dtype=np.float64),) * 3, indexing="ij"), -1).reshape(-1, 3)
+        pts = g[rng.permutation(len(g))]
+    elif kind == "duplicates":
+        pts = rng.random((N, 3)) * np.array([4.0, 3.0, 5.0])
+        sites = pts[rng.choice(N, 200, replace=False)]
+        pts[rng.choice(N, int(0.3 * N), replace=False)] = sites[rng.integers(0, 200, int(0.3 * N))]
+    elif kind == "identical":
+        pts = np.tile(np.array([[0.25, -1.5, 3.0]]), (N, 1))
+    elif kind == "cluster_far":
+        pts = 0.1 * rng.normal(size=(N, 3))
+        pts[rng.integers(N)] = (1e4, 0.0, 0.0)
+    elif kind == "offset_mm":
+        side = int(np.ceil((3 * N) ** (1.0 / 3.0)))
+        pts = rng.integers(0, side, (N, 3)) * 1e-3 + np.array([1000.0, -2000.0, 500.0])
+    elif kind == "collinear":
+        t = rng.random((N, 1)) * 10.0 - 5.0
+        pts = np.array([0.3, 0.1, 2.0]) + t * np.array([1.0, 2.0, -0.5])
+    elif kind == "nonfinite":
+        pts = rng.normal(size=(N, 3))
+        rows = rng.choice(N, max(3, N // 50), replace=False)
+        vals = np.array([np.nan, np.inf, -np.inf])
+        for k, r in enumerate(rows):
+            pts[r, rng.integers(0, 3) if k % 2 else slice(None)] = vals[k % 3]
+    else:
+        raise ValueError(kind)
+    return np.ascontiguousarray(pts, dtype=np.float32)
+
+
+KNN_KINDS = ("volume", "normal", "plane", "lattice", "duplicates", "identical", "cluster_far", "offset_mm", "collinear",
+             "nonfinite")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Loss inputs with pixels on the decision boundaries of oracle/loss_ref.py (float32, as the reference evaluates them).
+
+LOSS_KNIFE_EDGES = ("depth_far", "depth_near", "d_1e-5", "gt_1e-5", "silmask_th", "edge_thres", "d_eq_gt", "c_eq_gt")
+
+
+def loss_knife_inputs(W, H, use_weight_norm=True, seed=0, per=400, eps=1e-6, silmask_th=0.9, edge_thres=0.4,
+                      depth_near=1e-2, depth_far=1e2):
+    """A frame of loss inputs (random colours, alphas and depths with NaN / inf / out-of-range pixels, as test_loss._inputs)
+    with knife-edge pixels at random positions: for each boundary of LOSS_KNIFE_EDGES, `per` pixels one float32 ulp below
+    it, `per` exactly on it and `per` one ulp above it.  The weight-normalised depth d = D / (A + eps) is the float32 quotient
+    (D is searched so that it rounds to the target); without use_weight_norm d = D.  Knife-edge pixels are otherwise inside
+    every mask (alpha > silmask_th, valid depths).  Returns color [3,H,W], allmap [7,H,W], gt_color [H,W,3],
+    gt_depth [H,W,1] (float32 torch tensors) and {edge: flat pixel indices [3, per] (below, on, above)}."""
+    f = np.float32
+    rng = np.random.default_rng(seed)
+    HW = W * H
+    color = rng.random((3, HW)).astype(f)
+    alpha = rng.random(HW).astype(f)
+    alpha[rng.random(HW) < 0.2] = 0.0
+    allmap = np.zeros((7, HW), f)
+    allmap[0] = ((0.5 + 5 * rng.random(HW)) * alpha).astype(f)
+    allmap[1] = alpha
+    allmap[6] = (0.01 * rng.random(HW)).astype(f)
+    gt_color = rng.random((HW, 3)).astype(f)
+    gt_depth = (0.5 + 5 * rng.random(HW)).astype(f)
+    gt_depth[rng.random(HW) < 0.1] = 0.0
+    poison = rng.choice(HW, 30, replace=False)
+    allmap[0, poison[:5]] = np.nan; allmap[0, poison[5:10]] = np.inf; allmap[1, poison[10:15]] = np.nan
+    allmap[0, poison[15:20]] = 500.0; color[0, poison[20:25]] = np.nan; allmap[6, poison[25:]] = np.inf
+
+    ae32 = lambda A: (A + f(eps)).astype(f) if use_weight_norm else np.ones_like(A)
+    d32 = lambda D, A: (D / ae32(A)).astype(f) if use_weight_norm else D
+
+    def depth_for(q, A):
+        """D whose float32 d equals q (nan where no D within 4 ulps of q * (A + eps) rounds to q)."""
+        if not use_weight_norm:
+            return q.copy()
+        D0 = (q.astype(np.float64) * ae32(A)).astype(f)
+        out = np.full_like(q, np.nan)
+        for k in (0, -1, 1, -2, 2, -3, 3, -4, 4):
+            D = D0.copy()
+            for _ in range(abs(k)):
+                D = np.nextafter(D, f(np.inf) if k > 0 else f(-np.inf))
+            hit = np.isnan(out) & (d32(D, A) == q)
+            out[hit] = D[hit]
+        return out
+
+    def around(x):
+        x = np.asarray(x, f)
+        return np.stack([np.nextafter(x, f(-np.inf)), x, np.nextafter(x, f(np.inf))])
+
+    free = rng.permutation(HW)
+    edges, used = {}, 0
+    for edge in LOSS_KNIFE_EDGES:
+        pix = free[used:used + 3 * per].reshape(3, per)
+        used += 3 * per
+        edges[edge] = pix
+        for k in range(3):
+            p = pix[k]
+            A = (0.92 + 0.08 * rng.random(per)).astype(f)
+            q = (0.5 + 5 * rng.random(per)).astype(f)
+            gt = (0.5 + 5 * rng.random(per)).astype(f)
+            if edge in ("depth_far", "depth_near"):
+                A[per // 2:] = (0.05 + 0.85 * rng.random(per - per // 2)).astype(f)  # half outside the tracking mask
+                q = np.full(per, around(depth_far if edge == "depth_far" else depth_near)[k], f)
+            elif edge == "d_1e-5":
+                q = np.full(per, around(1e-5)[k], f)
+            elif edge == "gt_1e-5":
+                gt = np.full(per, around(1e-5)[k], f)
+            elif edge == "silmask_th":
+                A = np.full(per, around(silmask_th)[k], f)
+            elif edge == "edge_thres":
+                A = np.full(per, around(edge_thres)[k], f)
+            D = depth_for(q, A)
+            for _ in range(20):  # no float32 D gives exactly q for this A: draw that pixel's free value again
+                miss = np.isnan(D)
+                if not miss.any():
+                    break
+                if edge in ("silmask_th", "edge_thres"):
+                    q[miss] = (0.5 + 5 * rng.random(miss.sum())).astype(f)
+                else:
+                    A[miss] = (0.05 + 0.95 * rng.random(miss.sum())).astype(f)
+                D[miss] = depth_for(q[miss], A[miss])
+            assert not np.isnan(D).any()
+            if edge == "d_eq_gt":
+                gt = around(d32(D, A))[k]
+            allmap[0, p], allmap[1, p], gt_depth[p] = D, A, gt
+            allmap[6, p] = (0.01 * rng.random(per)).astype(f)
+            if edge == "c_eq_gt":
+                gt_color[p] = around(color[:, p].T)[k]
+    t = torch.from_numpy
+    return (t(color.reshape(3, H, W)), t(allmap.reshape(7, H, W)), t(gt_color.reshape(H, W, 3)),
+            t(gt_depth.reshape(H, W, 1)), edges)
