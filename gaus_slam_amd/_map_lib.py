@@ -1,0 +1,57 @@
+"""ctypes binding of the map growth / pruning C ABI (include/gs2d_map.h, libgs2d_map_hip.so).  Like _lib.py it fails loudly
+when the library is missing: there is no CPU fallback."""
+import ctypes as C
+import os
+
+from . import build as _build
+
+EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_select", "gs2d_map_seed_write",
+           "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_build_info", "gs2d_map_last_error"]
+MAX_ARRAYS = 16  # GS2D_MAP_MAX_ARRAYS
+WS_COUNT, WS_MEDIAN = 0, 1  # GS2D_MAP_WS_COUNT, GS2D_MAP_WS_MEDIAN: uint32 word offsets into a workspace
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is not None:
+        return _lib
+    path = _build.MAP_LIB_PATH
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"gaus_slam_amd: HIP library {path} is missing. Build it with `python -m gaus_slam_amd.build` "
+            "(needs hipcc); this package has no CPU fallback.")
+    import torch  # noqa: F401  (first, so that the process ends up with ONE HIP runtime: see _lib.lib)
+    L = C.CDLL(path)
+    vp, i, f, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+    L.gs2d_map_seed_ws_bytes.restype = sz
+    L.gs2d_map_seed_ws_bytes.argtypes = [i, i]
+    L.gs2d_map_prune_ws_bytes.restype = sz
+    L.gs2d_map_prune_ws_bytes.argtypes = [i]
+    L.gs2d_map_seed_select.restype = i
+    L.gs2d_map_seed_select.argtypes = [i, i, i, vp, vp, f, f, i, f, f, f, vp, vp]
+    L.gs2d_map_seed_write.restype = i
+    L.gs2d_map_seed_write.argtypes = [i, i, i, vp, vp, vp, f, f, f, f, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gs2d_map_prune_select.restype = i
+    L.gs2d_map_prune_select.argtypes = [i, vp, vp, i, f, f, f, vp, vp]
+    L.gs2d_map_compact.restype = i
+    L.gs2d_map_compact.argtypes = [i, vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp]
+    L.gs2d_map_build_info.restype = C.c_char_p
+    L.gs2d_map_last_error.restype = C.c_char_p
+    _lib = L
+    return L
+
+
+def last_error():
+    return lib().gs2d_map_last_error().decode()
+
+
+def build_info():
+    """gs2d_map_build_info(): flags, build date and the hash of csrc_map/ + gs2d_map.h the loaded library was compiled from."""
+    return lib().gs2d_map_build_info().decode()
+
+
+def lib_source_hash():
+    info = build_info()
+    return info.rsplit(" src ", 1)[1] if " src " in info else "unknown"

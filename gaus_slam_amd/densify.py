@@ -1,0 +1,256 @@
+"""Map growth and pruning on the device: the reference's slam/Densify.py (`add_new_gaussians` followed by
+`prune_gaussians`) on top of a GaussianSoA / FusedGaussianAdam.
+
+The reference runs this step at every keyframe and at every mapping start, in PyTorch: the add mask and a device-wide
+median (Densify.py:12-19), `get_pointcloud` (utils/common_utils.py:209-243: back-projection, validity mask, normals, initial
+scale), `add_gaussians_from_pcd` (scene/Gaussians.py:186-226: normal -> quaternion) and then boolean-index / cat over every
+parameter and both Adam moments.  Here it is four calls into libgs2d_map_hip.so (include/gs2d_map.h):
+
+    seed_select  -> n     (one host read: the new buffers have to be sized)
+    seed_write            (straight into the tail of the re-allocated flat buffer)
+    prune_select -> keep  (one host read)
+    compact               (parameters and both moments, 15 arrays, one launch)
+
+Selection (which pixels seed, which rows are pruned, the median) is bit-exact against the float32 PyTorch formulation;
+seed values are another float32 evaluation of the same formulas ("Map growth and pruning").  Two deliberate
+departures: seeds on the image border get the identity rotation (the reference leaves a `torch.rand_like` normal there,
+common_utils.py:184), and the `sample_num` subsampling of get_pointcloud (`random.sample`, common_utils.py:231-235) is not
+offered -- every configuration of the reference sets `num_addpts = h*w`, with which that branch is never taken.
+
+No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError."""
+import ctypes as C
+from collections import OrderedDict, namedtuple
+
+import torch
+
+from . import _map_lib
+from .ba_shard import BUCKET_FIELDS, BUCKET_FLOATS
+from .optim import _views
+from .rasterizer import _on_device, _stream_ptr
+
+MODES = {"splatam": 0, "edge": 1}
+
+# What seed_select leaves behind for seed_write: the seed count, the opaque device workspace and what it was computed for.
+SeedSelection = namedtuple("SeedSelection", "n ws mode width height")
+
+
+def _require(cond, msg):
+    if not cond:
+        raise RuntimeError(msg)
+
+
+def _check_tensor(t, name, shape=None, numel=None):
+    _require(isinstance(t, torch.Tensor), f"{name} must be a torch.Tensor")
+    _require(t.dtype == torch.float32, f"{name} must be float32, got {t.dtype}")
+    if shape is not None:
+        _require(tuple(t.shape) == tuple(shape), f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if numel is not None:
+        _require(t.numel() == numel, f"{name} must have {numel} elements, got shape {tuple(t.shape)}")
+    _require(t.is_contiguous(), f"{name} must be contiguous")
+
+
+def _check_frame(allmap, gt_color, gt_depth, device=True):
+    _require(isinstance(allmap, torch.Tensor) and allmap.dim() == 3 and allmap.shape[0] == 7,
+             "allmap must be the [7,H,W] rasterizer output")
+    H, W = int(allmap.shape[1]), int(allmap.shape[2])
+    _require(H >= 1 and W >= 1 and H * W <= 1 << 30, "allmap must have 1 <= H*W <= 2^30 pixels")
+    _check_tensor(allmap, "allmap")
+    if gt_color is not None:
+        _check_tensor(gt_color, "gt_color", shape=(H, W, 3))
+    _check_tensor(gt_depth, "gt_depth", numel=H * W)
+    _require(gt_depth.dim() >= 2 and tuple(gt_depth.shape[:2]) == (H, W), f"gt_depth must be [H,W] or [H,W,1] = [{H},{W}]")
+    for t, name in ((allmap, "allmap"), (gt_color, "gt_color"), (gt_depth, "gt_depth")):
+        if device and t is not None:
+            _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
+            _require(t.device == allmap.device, f"{name} must be on {allmap.device}")
+    return W, H
+
+
+def _intrinsics(intrinsics):
+    """(fx, fy, cx, cy) as Python floats from a [3,3] matrix (tensor, array or nested list).  A device tensor costs one host
+    read; pass a host tensor to avoid it."""
+    k = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32)
+    _require(tuple(k.shape) == (3, 3), f"intrinsics must be a [3,3] matrix, got {tuple(k.shape)}")
+    return float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+
+
+def c2w_from_w2c(w2c):
+    """The camera-to-world matrix the seeds are placed with: torch.linalg.inv(w2c) as get_pointcloud does it
+    (common_utils.py:211-212), contiguous float32 [4,4] on the device of w2c."""
+    _require(isinstance(w2c, torch.Tensor) and tuple(w2c.shape) == (4, 4), "w2c must be a [4,4] tensor")
+    _require(w2c.is_cuda, "w2c must be a CUDA tensor (no CPU fallback)")
+    return torch.linalg.inv(w2c.detach().float()).contiguous()
+
+
+def seed_select(allmap, gt_depth, *, mode="splatam", sil_thres, edge_thres=0.4, use_weight_norm=True, eps=1e-6, depth_near=1e-2,
+                depth_far=1e2):
+    """Which pixels seed a Gaussian (gs2d_map_seed_select).  Returns a SeedSelection; `.n` is the seed count (one host read).
+    mode "splatam": Densify.py:16-19 (silhouette below sil_thres, or the render behind gt by more than 50 medians of the depth
+    error); mode "edge": Densify.py:29-31.  Both are ANDed with the validity mask of get_pointcloud."""
+    _require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    W, H = _check_frame(allmap, None, gt_depth)
+    dev = allmap.device
+    L = _map_lib.lib()
+    ws = torch.empty(L.gs2d_map_seed_ws_bytes(W, H), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        n = L.gs2d_map_seed_select(MODES[mode], W, H, allmap.data_ptr(), gt_depth.data_ptr(), float(sil_thres), float(edge_thres),
+                                   int(bool(use_weight_norm)), float(eps), float(depth_near), float(depth_far), ws.data_ptr(),
+                                   _stream_ptr(dev))
+    if n < 0:
+        raise RuntimeError(_map_lib.last_error())
+    return SeedSelection(n, ws, mode, W, H)
+
+
+def seed_median(sel):
+    """The lower median of the depth error that a "splatam" selection compared against, as a 0-dim float32 device tensor: word
+    GS2D_MAP_WS_MEDIAN of the workspace (include/gs2d_map.h)."""
+    _require(sel.mode == "splatam", "only a splatam selection computes a median")
+    o = 4 * _map_lib.WS_MEDIAN
+    return sel.ws[o:o + 4].view(torch.float32)[0]
+
+
+def seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pixel_index=None, activated=False):
+    """Writes the seeds of `sel` into `out`, a dict of BUCKET_FIELDS names to contiguous float32 [n,k] tensors (e.g. the tails
+    of a re-allocated SoA); pixel_index: int32 [n] or None (gs2d_map_seed_write)."""
+    W, H = _check_frame(allmap, gt_color, gt_depth)
+    _require((W, H) == (sel.width, sel.height), "the selection was computed for another image size")
+    dev = allmap.device
+    for name, k in BUCKET_FIELDS.items():
+        _check_tensor(out[name], f"out[{name!r}]", shape=(sel.n, k))
+        _require(out[name].device == dev, f"out[{name!r}] must be on {dev}")
+    if pixel_index is not None:
+        _require(pixel_index.dtype == torch.int32 and tuple(pixel_index.shape) == (sel.n,) and pixel_index.is_contiguous()
+                 and pixel_index.device == dev, "pixel_index must be a contiguous int32 [n] tensor on the frame's device")
+    _check_tensor(c2w, "c2w", shape=(4, 4))
+    _require(c2w.device == dev, f"c2w must be on {dev}")
+    fx, fy, cx, cy = _intrinsics(intrinsics)
+    if sel.n == 0:
+        return
+    with _on_device(dev):
+        rc = _map_lib.lib().gs2d_map_seed_write(
+            MODES[sel.mode], W, H, allmap.data_ptr(), gt_color.data_ptr(), gt_depth.data_ptr(), fx, fy, cx, cy, c2w.data_ptr(),
+            int(bool(activated)), sel.ws.data_ptr(), out["means3D"].data_ptr(), out["opacities"].data_ptr(),
+            out["scales"].data_ptr(), out["rotations"].data_ptr(), out["colors"].data_ptr(),
+            None if pixel_index is None else pixel_index.data_ptr(), _stream_ptr(dev))
+    if rc < 0:
+        raise RuntimeError(_map_lib.last_error())
+
+
+def seed_from_frame(allmap, gt_color, gt_depth, intrinsics, w2c, *, mode="splatam", sil_thres, edge_thres=0.4,
+                    use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2, activated=False):
+    """New Gaussians from one rendered view and its RGB-D frame: the add mask of Densify.py, get_pointcloud and the
+    initialisation of add_gaussians_from_pcd.
+
+    allmap: raw [7,H,W] rasterizer output; gt_color: [H,W,3]; gt_depth: [H,W] (or [H,W,1]); intrinsics: [3,3]; w2c: [4,4].
+    Returns an OrderedDict with the BUCKET_FIELDS names (means3D [n,3], opacities [n,1], scales [n,2], rotations [n,4],
+    colors [n,3]; raw values, or activated ones with activated=True) plus `pixel_index` (int32 [n], y*W + x), seeds in row-major
+    pixel order.  The `sample_num` subsampling of get_pointcloud is not offered (see the module docstring)."""
+    _require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    _check_frame(allmap, gt_color, gt_depth, device=False)  # shapes and dtypes first, devices second
+    _intrinsics(intrinsics)
+    _check_frame(allmap, gt_color, gt_depth)
+    c2w = c2w_from_w2c(w2c)
+    sel = seed_select(allmap, gt_depth, mode=mode, sil_thres=sil_thres, edge_thres=edge_thres, use_weight_norm=use_weight_norm,
+                      eps=eps, depth_near=depth_near, depth_far=depth_far)
+    dev = allmap.device
+    out = OrderedDict((name, torch.empty((sel.n, k), dtype=torch.float32, device=dev)) for name, k in BUCKET_FIELDS.items())
+    pix = torch.empty(sel.n, dtype=torch.int32, device=dev)
+    seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pix, activated)
+    out["pixel_index"] = pix
+    return out
+
+
+def _check_opt(opt):
+    soa = opt.soa
+    _require(soa.flat.is_cuda, "the Gaussian SoA must live on a CUDA device (no CPU fallback)")
+    _require(opt.exp_avg.numel() == soa.flat.numel() and opt.exp_avg_sq.numel() == soa.flat.numel(),
+             "optimizer moments do not match the SoA")
+
+
+def _adopt(opt, flat, exp_avg, exp_avg_sq, P):
+    """Hands re-allocated buffers to the SoA and its optimizer: what FusedGaussianAdam._rebuild ends in, without the copies."""
+    soa = opt.soa
+    soa.generation = soa.generation + 1
+    soa.P = P
+    soa.flat = flat
+    soa.views = _views(flat, P)
+    opt.exp_avg, opt.exp_avg_sq = exp_avg, exp_avg_sq
+
+
+def _grow(opt, n_new):
+    """Re-allocates parameters and moments for P + n_new rows: old rows copied, new parameter rows left for seed_write, new
+    moment rows zero (cat_tensors_to_optimizer, scene/Gaussians.py:162-184).  Returns the [P+n,k] parameter views."""
+    soa = opt.soa
+    P, Pn = soa.P, soa.P + n_new
+    flat = torch.empty(BUCKET_FLOATS * Pn, dtype=torch.float32, device=soa.flat.device)
+    m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+    for new, old in ((flat, soa.flat), (m, opt.exp_avg), (v, opt.exp_avg_sq)):
+        for nv, ov in zip(_views(new, Pn).values(), _views(old, P).values()):
+            nv[:P].copy_(ov)
+    _adopt(opt, flat, m, v, Pn)
+    return soa.views
+
+
+def prune_gaussians(opt, opacity_cull, scale_cull, scale_max, activated=False):
+    """Densify.prune_gaussians (Densify.py:43-50) on a FusedGaussianAdam: rows with sigmoid(opacity) < opacity_cull, or a mean
+    exp(scale) below scale_cull or above scale_max are removed from the parameters and both moments (activated=True: the
+    stored values are compared as they are).  One select (one host read) and one compaction launch for all 15 arrays.  The
+    flat buffer is re-allocated and `soa.generation` bumped as FusedGaussianAdam.prune does.  Returns the number of rows removed."""
+    _check_opt(opt)
+    soa = opt.soa
+    P, dev = soa.P, soa.flat.device
+    L = _map_lib.lib()
+    ws = torch.empty(max(int(L.gs2d_map_prune_ws_bytes(P)), 4), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        n_keep = L.gs2d_map_prune_select(P, soa.views["opacities"].data_ptr(), soa.views["scales"].data_ptr(), int(bool(activated)),
+                                         float(opacity_cull), float(scale_cull), float(scale_max), ws.data_ptr(), _stream_ptr(dev))
+    if n_keep < 0:
+        raise RuntimeError(_map_lib.last_error())
+    new = [torch.empty(BUCKET_FLOATS * n_keep, dtype=torch.float32, device=dev) for _ in range(3)]
+    src, dst, widths = [], [], []
+    for nb, ob in zip(new, (soa.flat, opt.exp_avg, opt.exp_avg_sq)):
+        for (name, nv), ov in zip(_views(nb, n_keep).items(), _views(ob, P).values()):
+            src.append(ov.data_ptr()); dst.append(nv.data_ptr()); widths.append(BUCKET_FIELDS[name])
+    n = len(src)
+    with _on_device(dev):
+        rc = L.gs2d_map_compact(P, ws.data_ptr(), n, (C.c_void_p * n)(*src), (C.c_void_p * n)(*dst), (C.c_int * n)(*widths),
+                                _stream_ptr(dev))
+    if rc < 0:
+        raise RuntimeError(_map_lib.last_error())
+    _adopt(opt, new[0], new[1], new[2], n_keep)
+    return P - n_keep
+
+
+def add_new_gaussians(opt, allmap, gt_color, gt_depth, intrinsics, w2c, densify_cfg, render_cfg, activated=False):
+    """The whole of Densify.add_new_gaussians (Densify.py:8-41) on a FusedGaussianAdam: splatam seeding, edge-growth seeding
+    when densify_cfg['use_edge_growth'], then prune_gaussians.  `allmap` is the view rendered BEFORE the call, as in the
+    reference, where both seedings read the same render_pkg.
+
+    densify_cfg: sil_thres, edge_thres, use_edge_growth, opacity_cuil, scale_cuil, scale_max (the reference's spelling;
+    opacity_cull / scale_cull are accepted too); render_cfg: use_weight_norm, eps, depth_near, depth_far.
+    Seeds are written straight into the tail of the re-allocated flat buffer, their moments are zero, and `soa.generation` is
+    bumped as FusedGaussianAdam.cat / prune do.  `num_addpts` is not read: the `sample_num` subsampling is not offered (every
+    reference configuration sets num_addpts = h*w, which never subsamples).  Returns (n_added, n_pruned)."""
+    _check_opt(opt)
+    _check_frame(allmap, gt_color, gt_depth)
+    _require(allmap.device == opt.soa.flat.device, "the frame and the Gaussian SoA must be on one device")
+    method = densify_cfg.get("method", "splatam")
+    _require(method == "splatam", f"densify method {method!r} is not supported (every reference configuration uses 'splatam')")
+    c2w = c2w_from_w2c(w2c)
+    depth = dict(use_weight_norm=render_cfg.get("use_weight_norm", True), eps=render_cfg.get("eps", 1e-6),
+                 depth_near=render_cfg.get("depth_near", 1e-2), depth_far=render_cfg.get("depth_far", 1e2))
+    thres = dict(sil_thres=densify_cfg["sil_thres"], edge_thres=densify_cfg.get("edge_thres", 0.4))
+    sels = [seed_select(allmap, gt_depth, mode="splatam", **thres, **depth)]
+    if densify_cfg.get("use_edge_growth", False):
+        sels.append(seed_select(allmap, gt_depth, mode="edge", **thres, **depth))
+    n_added = sum(s.n for s in sels)
+    if n_added:
+        row = opt.soa.P
+        views = _grow(opt, n_added)
+        for s in sels:
+            seed_write(s, allmap, gt_color, gt_depth, intrinsics, c2w,
+                       {name: v[row:row + s.n] for name, v in views.items()}, None, activated)
+            row += s.n
+    cull = lambda k: densify_cfg[k + "_cuil"] if k + "_cuil" in densify_cfg else densify_cfg[k + "_cull"]
+    n_pruned = prune_gaussians(opt, cull("opacity"), cull("scale"), densify_cfg["scale_max"], activated)
+    return n_added, n_pruned

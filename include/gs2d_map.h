@@ -1,0 +1,105 @@
+/*
+ * gs2d_map.h -- C ABI of the map growth / pruning kernels (libgs2d_map_hip.so, sources in gaus_slam_amd/csrc_map/).
+ *
+ * The step the reference runs at every keyframe and every mapping start (slam/Densify.py: add_new_gaussians followed by
+ * prune_gaussians), as four device calls:
+ *
+ *   gs2d_map_seed_select  <- Densify.py:12-19,30-31 (the add mask) AND utils/common_utils.py:87-103 (the validity mask of
+ *                            get_pointcloud); returns the number of seeds
+ *   gs2d_map_seed_write   <- common_utils.py:122-145,148-160,174-207 (back-projection, normals, initial scale) and
+ *                            scene/Gaussians.py:186-226 (normal -> quaternion, raw opacity 0, log scale)
+ *   gs2d_map_prune_select <- Densify.py:43-49 (the prune mask); returns the number of rows kept
+ *   gs2d_map_compact      <- scene/Gaussians.py:143-160 (parameters AND both Adam moments, in one launch)
+ *
+ * Conventions follow gs2d_rasterizer.h: device pointers to float32 / int32 data in plain C layouts, `stream` is a
+ * hipStream_t (NULL = the null stream), a return value < 0 signals an error that gs2d_map_last_error() describes, and no
+ * torch type appears here.  Workspaces are allocated by the caller (4-byte aligned at least, any content) and sized by
+ * gs2d_map_seed_ws_bytes / gs2d_map_prune_ws_bytes; a workspace carries the selection from the *_select call to the
+ * *_write / compact call on the same stream and may be reused afterwards.  The two *_select calls end with ONE 4-byte
+ * device-to-host read and a wait on `stream` (the caller has to size the new buffers); nothing else synchronises.
+ *
+ * Exactness.  The library is built with -ffp-contract=off and every quotient is a correctly rounded float32 division, so
+ * each selection decision is the IEEE float32 comparison PyTorch makes on the same inputs: the seed list and the median
+ * are equal to the reference's bit for bit.  Seed VALUES are another float32 evaluation of the same formulas, except the
+ * normal: the neighbour points, their two differences and the cross product are evaluated in float64 on the float32 inputs
+ * (the differences cancel most of the points' leading bits), the frame and the quaternion in float32 again.
+ *
+ * Out of contract: non-finite gt_depth (the reference multiplies a mask by |d - gt|, which turns an infinity into NaN and
+ * poisons its median).  Non-finite rasterizer output is handled as nan_to_num(., 0, 0) handles it.
+ *
+ * Deliberate departures from the reference:
+ *   - Seeds on the image border (x or y on the first / last column / row).  The reference leaves the normal of those pixels
+ *     at torch.rand_like (common_utils.py:184), so their rotation is random there.  Here they get the identity quaternion.
+ *   - sample_num subsampling (random.sample, common_utils.py:231-235) is not offered: every configuration of the reference
+ *     sets num_addpts = h*w, with which that branch is never taken.
+ */
+#ifndef GS2D_MAP_H
+#define GS2D_MAP_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Word (uint32) offsets into either workspace that a caller may read back after the *_select call. */
+#define GS2D_MAP_WS_COUNT 0   /* number of seeds / of rows kept (what the *_select call returned) */
+#define GS2D_MAP_WS_MEDIAN 1  /* seed workspace, mode 0: bit pattern of the lower median of the depth error */
+
+#define GS2D_MAP_MODE_SPLATAM 0
+#define GS2D_MAP_MODE_EDGE 1
+
+size_t gs2d_map_seed_ws_bytes(int width, int height);
+size_t gs2d_map_prune_ws_bytes(int P);
+
+/* Which pixels of a rendered view seed a new Gaussian.  allmap: the raw [7,H,W] rasterizer output (channel 0 the depth sum
+ * D, channel 1 the accumulated alpha A), gt_depth: [H,W].  The rendered depth is d = D / (A + eps) zeroed outside
+ * [depth_near, depth_far] (use_weight_norm = 0: d = D), then nan_to_num(d, 0, 0) (render/__init__.py:129-132,
+ * Densify.py:14).
+ *   mode 0 ("splatam"):     err = gt > 0 ? |d - gt| : 0;  med = element of rank (HW-1)/2 of sorted err (torch.median);
+ *                           add = (A < sil_thres) | ((d > gt) & (err > 50 med));  source depth z = gt
+ *   mode 1 ("edge growth"): add = (A > edge_thres) & (A < sil_thres) & (gt < 0.001);  z = d
+ * Either is ANDed with the validity mask 0.01 < z < 15 at the pixel and at each of its in-image 3x3 neighbours.
+ * Returns the number of seeds (>= 0). */
+int gs2d_map_seed_select(int mode, int width, int height, const float* allmap, const float* gt_depth, float sil_thres,
+                         float edge_thres, int use_weight_norm, float eps, float depth_near, float depth_far, void* ws,
+                         void* stream);
+
+/* Writes the n seeds a gs2d_map_seed_select call with the same mode / size / allmap / gt_depth left in `ws`, in row-major
+ * pixel order (the order pts.reshape(-1,3)[mask] gives).  The five output pointers address row 0 of the n new rows of
+ * [n,3] [n,1] [n,2] [n,4] [n,3] arrays -- typically the tails of a re-allocated structure of arrays; pixel_index is [n] int32 (y*W + x of every seed) or NULL.  gt_color_hwc: [H,W,3].  c2w: 16 floats, row-major, on the device (the caller
+ * inverts w2c).  Per seed:
+ *   means3D   = c2w (((x-cx)/fx) z, ((y-cy)/fy) z, z, 1), the three products summed in index order
+ *   colors    = gt_color[y,x,:], a bit copy
+ *   opacities = 0 (activated: 0.5);   scales = log(z / ((fx+fy)/2)) twice (activated: z / ((fx+fy)/2))
+ *   rotations = matrix_to_quaternion([v0 v1 v2]) of the look-at frame of the normal
+ *               n = normalize(cross(P[y+1,x] - P[y-1,x], P[y,x+1] - P[y,x-1])) over the WORLD points of the four neighbours,
+ *               up = (ny nz, nx nz, -2 nx ny), then nan_to_num(., 0, 0) and (1,0,0,0) when the norm is < 1e-3 (a normal along
+ *               a coordinate axis: up = 0); (1,0,0,0) on the image border (see "departures" above).
+ * Mode 1 reads its source depth z = d from `ws`, where the select call left it. */
+int gs2d_map_seed_write(int mode, int width, int height, const float* allmap, const float* gt_color_hwc, const float* gt_depth,
+                        float fx, float fy, float cx, float cy, const float* c2w, int activated, const void* ws, float* means3D,
+                        float* opacities, float* scales, float* rotations, float* colors, int* pixel_index, void* stream);
+
+/* Which rows survive pruning: a row is REMOVED when sigmoid(o) < opacity_cull, or m < scale_cull, or m > scale_max with
+ * m = (exp(s0) + exp(s1)) * 0.5f.  opacities: [P,1], scales: [P,2].  activated = 1: the values are compared as they are.
+ * Returns the number of rows kept (>= 0). */
+int gs2d_map_prune_select(int P, const float* opacities, const float* scales, int activated, float opacity_cull,
+                          float scale_cull, float scale_max, void* ws, void* stream);
+
+/* Copies the rows gs2d_map_prune_select kept from each src[a] ([P, widths[a]] floats) to dst[a] ([n_keep, widths[a]]), order
+ * preserved, all arrays in one launch.  src / dst / widths are HOST arrays of n_arrays <= GS2D_MAP_MAX_ARRAYS entries,
+ * 1 <= widths[a] <= 4; src[a] and dst[a] must not overlap. */
+#define GS2D_MAP_MAX_ARRAYS 16
+int gs2d_map_compact(int P, const void* ws, int n_arrays, const float* const* src, float* const* dst, const int* widths,
+                     void* stream);
+
+/* "... src <hash>": the hash of csrc_map/ + this header the library was built from (gaus_slam_amd/build.py). */
+const char* gs2d_map_build_info(void);
+const char* gs2d_map_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
