@@ -6,9 +6,12 @@ import os
 from . import build as _build
 
 EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_select", "gs2d_map_seed_write",
-           "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_build_info", "gs2d_map_last_error"]
+           "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_densify_stats", "gs2d_map_densify_ws_bytes",
+           "gs2d_map_densify_select", "gs2d_map_densify_write", "gs2d_map_build_info", "gs2d_map_last_error"]
 MAX_ARRAYS = 16  # GS2D_MAP_MAX_ARRAYS
 WS_COUNT, WS_MEDIAN = 0, 1  # GS2D_MAP_WS_COUNT, GS2D_MAP_WS_MEDIAN: uint32 word offsets into a workspace
+# GS2D_MAP_WS_DENSIFY_*: what gs2d_map_densify_select copies to its `counts` argument
+WS_DENSIFY_OLD, WS_DENSIFY_CLONES, WS_DENSIFY_CHILDREN, WS_DENSIFY_N_CLONED, WS_DENSIFY_N_SPLIT, WS_DENSIFY_WORDS = 2, 3, 4, 5, 6, 8
 
 _lib = None
 
@@ -37,6 +40,14 @@ def lib():
     L.gs2d_map_prune_select.argtypes = [i, vp, vp, i, f, f, f, vp, vp]
     L.gs2d_map_compact.restype = i
     L.gs2d_map_compact.argtypes = [i, vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp]
+    L.gs2d_map_densify_stats.restype = i
+    L.gs2d_map_densify_stats.argtypes = [i, vp, vp, vp, vp, vp]
+    L.gs2d_map_densify_ws_bytes.restype = sz
+    L.gs2d_map_densify_ws_bytes.argtypes = [i]
+    L.gs2d_map_densify_select.restype = i
+    L.gs2d_map_densify_select.argtypes = [i, vp, vp, vp, vp, f, f, f, f, f, vp, C.POINTER(C.c_uint32), vp]
+    L.gs2d_map_densify_write.restype = i
+    L.gs2d_map_densify_write.argtypes = [i, vp, vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp]
     L.gs2d_map_build_info.restype = C.c_char_p
     L.gs2d_map_last_error.restype = C.c_char_p
     _lib = L

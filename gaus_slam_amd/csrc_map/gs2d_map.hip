@@ -12,6 +12,7 @@
 //   seed_write:          one kernel (block-local scan of the flags + the scanned block counts -> row, then the seed)
 //   prune_select:        flags + block counts | scan of block counts
 //   compact:             one kernel for all arrays (block-local list of kept rows in LDS, coalesced stores per array)
+// (densification from view-space gradients -- clone, split, prune in one select and one write -- is gs2d_map_densify.hip)
 // The median is an exact most-significant-digit-first radix select on the bit patterns of err (err >= 0, so unsigned order is
 // float order): four 8-bit digits, per-workgroup LDS histograms, one global add per non-empty bin per workgroup.  The
 // "which bin holds the rank" step between two digits is not a kernel of its own: every workgroup of the NEXT kernel redoes it
@@ -410,6 +411,10 @@ int read_count(const void* ws, hipStream_t s, const char* what)
 bool bad_size(int W, int H) { return W < 1 || H < 1 || (long long)W * H > (1ll << 30); }
 
 }  // namespace
+
+// the error text of this thread, for the other sources of the library (gs2d_map_densify.hip); not part of the C ABI
+__attribute__((visibility("hidden"))) int gs2d_map_fail(const char* msg) { return fail(msg); }
+__attribute__((visibility("hidden"))) int gs2d_map_fail_hip(const char* what, hipError_t e) { return fail_hip(what, e); }
 
 #ifndef GS2D_MAP_SOURCE_HASH
 #define GS2D_MAP_SOURCE_HASH "unknown"   /* gaus_slam_amd/build.py passes the hash of csrc_map/ + the C-ABI header */

@@ -17,6 +17,10 @@ departures: seeds on the image border get the identity rotation (the reference l
 common_utils.py:184), and the `sample_num` subsampling of get_pointcloud (`random.sample`, common_utils.py:231-235) is not
 offered -- every configuration of the reference sets `num_addpts = h*w`, with which that branch is never taken.
 
+The optimisation half of map maintenance is here too: `DensificationStats` (the reference's add_densification_stats,
+scene/Gaussians.py:58-62) and `densify_and_prune` (Gaussians.py:513-593: clone, split, prune from the accumulated view-space
+gradients), one select with one host read and one write launch.
+
 No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError."""
 import ctypes as C
 from collections import OrderedDict, namedtuple
@@ -254,3 +258,122 @@ def add_new_gaussians(opt, allmap, gt_color, gt_depth, intrinsics, w2c, densify_
     cull = lambda k: densify_cfg[k + "_cuil"] if k + "_cuil" in densify_cfg else densify_cfg[k + "_cull"]
     n_pruned = prune_gaussians(opt, cull("opacity"), cull("scale"), densify_cfg["scale_max"], activated)
     return n_added, n_pruned
+
+
+# ------------------------------------------------------------------------------- densification from view-space gradients
+# What densify_and_prune did: rows cloned and rows split (before the prune), rows the prune removed (old rows, clones and
+# children alike: P + n_cloned + n_split - P_new), and the new row count.
+DensifyResult = namedtuple("DensifyResult", "n_cloned n_split n_pruned P_new")
+
+
+class DensificationStats:
+    """The reference's `xyz_gradient_accum` / `denom` (scene/Gaussians.py:50-51) for the map of a FusedGaussianAdam: `accum`
+    and `denom`, float32 [P] on the map's device.
+
+    `add(radii, means2D_grad)` is add_densification_stats (Gaussians.py:58-62), one call per rendered view -- with
+    render_batch, one per view's own gradient carrier.  The statistics belong to one row layout:
+    whenever `soa.generation` has moved (add_new_gaussians, prune_gaussians, cat, prune, densify_and_prune) they are all-zero
+    at the new P on next use, as the reference re-creates them in add_params / remove_gaussians_from_mask /
+    densification_postfix."""
+
+    def __init__(self, opt):
+        self.opt = opt
+        self.accum = self.denom = None
+        self._generation = None
+
+    def reset(self):
+        """All-zero statistics for the map as it is now (one allocation, one memset)."""
+        soa = self.opt.soa
+        both = torch.zeros(2 * soa.P, dtype=torch.float32, device=soa.flat.device)
+        self.accum, self.denom = both[:soa.P], both[soa.P:]
+        self._generation = soa.generation
+
+    def current(self):
+        """The statistics of the present row layout: re-zeroed first when the map was re-allocated since the last use."""
+        if self._generation != self.opt.soa.generation or self.accum.shape[0] != self.opt.soa.P:
+            self.reset()
+        return self.accum, self.denom
+
+    def add(self, radii, means2D_grad):
+        """radii: int32 [P] as the operator returns it; means2D_grad: float32 [P,3], `means2D.grad` of that view.  For
+        radii > 0: accum += |grad[:, :2]|, denom += 1 (gs2d_map_densify_stats: one launch, no host read)."""
+        soa = self.opt.soa
+        P = soa.P
+        _require(isinstance(radii, torch.Tensor) and radii.dtype == torch.int32, "radii must be an int32 tensor")
+        _require(tuple(radii.shape) == (P,), f"radii must have shape ({P},), got {tuple(radii.shape)}")
+        _require(radii.is_contiguous(), "radii must be contiguous")
+        _check_tensor(means2D_grad, "means2D_grad", shape=(P, 3))
+        _check_opt(self.opt)
+        dev = soa.flat.device
+        for t, name in ((radii, "radii"), (means2D_grad, "means2D_grad")):
+            _require(t.is_cuda and t.device == dev, f"{name} must be a CUDA tensor on {dev} (no CPU fallback)")
+        accum, denom = self.current()
+        with _on_device(dev):
+            rc = _map_lib.lib().gs2d_map_densify_stats(P, radii.data_ptr(), means2D_grad.data_ptr(), accum.data_ptr(),
+                                                       denom.data_ptr(), _stream_ptr(dev))
+        if rc < 0:
+            raise RuntimeError(_map_lib.last_error())
+
+
+def _densify_thresholds(cfg):
+    """(T, D, opacity_cull, scale_cull, M) of densify_and_prune (Gaussians.py:576-590) as Python floats: the products are
+    formed in double here and rounded ONCE to float32 at the C ABI, which is what torch's comparison with a Python scalar does.
+    M = 0 switches the world-size clause off (`if max_screen_size:`)."""
+    for k in ("densify_grad_threshold", "percent_dense", "extent", "scale_max"):
+        _require(k in cfg, f"densify_cfg lacks {k!r}")
+    cull = lambda k: cfg[k + "_cuil"] if k + "_cuil" in cfg else cfg[k + "_cull"]
+    T, extent = float(cfg["densify_grad_threshold"]), float(cfg["extent"])
+    _require(C.c_float(T).value > 0, f"densify_grad_threshold must be > 0 in float32, got {T!r}: with T <= 0 the reference "
+                                     "splits the clones it has just appended, which this step does not reproduce")
+    _require(extent > 0 and extent != float("inf"), f"extent must be positive and finite, got {extent!r}")
+    return T, float(cfg["percent_dense"]) * extent, float(cull("opacity")), float(cull("scale")), (0.1 * extent if cfg["scale_max"] else 0.0)
+
+
+def densify_and_prune(opt, stats, densify_cfg, generator=None):
+    """Gaussians.densify_and_prune (scene/Gaussians.py:575-591: clone, split with N = 2, prune) on a FusedGaussianAdam, from
+    the statistics `stats` (a DensificationStats of `opt`) gathered since the last topology change.  Raw parameters only.
+
+    densify_cfg: densify_grad_threshold, percent_dense, extent, opacity_cuil, scale_cuil (or the _cull spellings), scale_max
+    (only its truth value is read: the reference's `max_radii2D > scale_max` clause is dead, include/gs2d_map.h).
+    generator: a torch.Generator ON THE MAP'S DEVICE (or None: the device's default generator) for the [P,2,2] standard
+    normals that place the children; the same seed gives the same map bit for bit.
+
+    One select (the call's only host read) and one write launch for all 15 arrays (include/gs2d_map.h).  Final rows: old rows
+    neither split nor pruned (with their moments), then surviving clones, first children, second children (zero moments).  The
+    buffers are re-allocated even when nothing changes, `soa.generation` is bumped (stale leaves raise in
+    FusedGaussianAdam.step) and `stats` is reset.  Returns DensifyResult(n_cloned, n_split, n_pruned, P_new)."""
+    T, D, opacity_cull, scale_cull, M = _densify_thresholds(densify_cfg)
+    _require(isinstance(stats, DensificationStats) and stats.opt is opt, "stats must be the DensificationStats of this optimizer")
+    _check_opt(opt)
+    soa = opt.soa
+    P, dev = soa.P, soa.flat.device
+    accum, denom = stats.current()
+    L = _map_lib.lib()
+    ws = torch.empty(max(int(L.gs2d_map_densify_ws_bytes(P)), 4), dtype=torch.uint8, device=dev)
+    noise = torch.randn((P, 2, 2), generator=generator, dtype=torch.float32, device=dev)
+    counts = (C.c_uint32 * _map_lib.WS_DENSIFY_WORDS)()
+    with _on_device(dev):
+        P_new = L.gs2d_map_densify_select(P, soa.views["opacities"].data_ptr(), soa.views["scales"].data_ptr(), accum.data_ptr(),
+                                          denom.data_ptr(), T, D, opacity_cull, scale_cull, M, ws.data_ptr(), counts, _stream_ptr(dev))
+    if P_new < 0:
+        raise RuntimeError(_map_lib.last_error())
+    n_cloned, n_split = int(counts[_map_lib.WS_DENSIFY_N_CLONED]), int(counts[_map_lib.WS_DENSIFY_N_SPLIT])
+    new = [torch.empty(BUCKET_FLOATS * P_new, dtype=torch.float32, device=dev) for _ in range(3)]
+    ptrs = lambda buf, n: [v.data_ptr() for v in _views(buf, n).values()]
+    vp5, n_mom = C.c_void_p * len(BUCKET_FIELDS), 2 * len(BUCKET_FIELDS)
+    vpm = C.c_void_p * n_mom
+    with _on_device(dev):
+        rc = L.gs2d_map_densify_write(P, ws.data_ptr(), noise.data_ptr(), vp5(*ptrs(soa.flat, P)), vp5(*ptrs(new[0], P_new)), n_mom,
+                                      vpm(*(ptrs(opt.exp_avg, P) + ptrs(opt.exp_avg_sq, P))),
+                                      vpm(*(ptrs(new[1], P_new) + ptrs(new[2], P_new))),
+                                      (C.c_int * n_mom)(*(2 * list(BUCKET_FIELDS.values()))), _stream_ptr(dev))
+    if rc < 0:
+        raise RuntimeError(_map_lib.last_error())
+    # The write kernel still reads the old buffers on this stream; when they were allocated on another one, the caching
+    # allocator must not hand them out there before it has finished.
+    stream = torch.cuda.current_stream(dev)
+    for old in (soa.flat, opt.exp_avg, opt.exp_avg_sq, accum):
+        old.record_stream(stream)
+    _adopt(opt, new[0], new[1], new[2], P_new)
+    stats.reset()
+    return DensifyResult(n_cloned, n_split, P + n_cloned + n_split - P_new, P_new)

@@ -11,12 +11,16 @@
  *   gs2d_map_prune_select <- Densify.py:43-49 (the prune mask); returns the number of rows kept
  *   gs2d_map_compact      <- scene/Gaussians.py:143-160 (parameters AND both Adam moments, in one launch)
  *
+ * and the step its backend runs inside every mapping / bundle-adjustment iteration (scene/Gaussians.py:58-62,513-593:
+ * add_densification_stats, densify_and_prune), as gs2d_map_densify_stats / _select / _write, described further down.
+ *
  * Conventions follow gs2d_rasterizer.h: device pointers to float32 / int32 data in plain C layouts, `stream` is a
  * hipStream_t (NULL = the null stream), a return value < 0 signals an error that gs2d_map_last_error() describes, and no
  * torch type appears here.  Workspaces are allocated by the caller (4-byte aligned at least, any content) and sized by
- * gs2d_map_seed_ws_bytes / gs2d_map_prune_ws_bytes; a workspace carries the selection from the *_select call to the
- * *_write / compact call on the same stream and may be reused afterwards.  The two *_select calls end with ONE 4-byte
- * device-to-host read and a wait on `stream` (the caller has to size the new buffers); nothing else synchronises.
+ * gs2d_map_seed_ws_bytes / gs2d_map_prune_ws_bytes / gs2d_map_densify_ws_bytes; a workspace carries the selection from the
+ * *_select call to the *_write / compact call on the same stream and may be reused afterwards.  Every *_select call ends
+ * with ONE small device-to-host read and a wait on `stream` (the caller has to size the new buffers); nothing else
+ * synchronises.
  *
  * Exactness.  The library is built with -ffp-contract=off and every quotient is a correctly rounded float32 division, so
  * each selection decision is the IEEE float32 comparison PyTorch makes on the same inputs: the seed list and the median
@@ -94,6 +98,64 @@ int gs2d_map_prune_select(int P, const float* opacities, const float* scales, in
 #define GS2D_MAP_MAX_ARRAYS 16
 int gs2d_map_compact(int P, const void* ws, int n_arrays, const float* const* src, float* const* dst, const int* widths,
                      void* stream);
+
+/* ---- Densification from view-space gradients: what the reference's backend does in every mapping / bundle-adjustment
+ * iteration (scene/Gaussians.py): add_densification_stats (:58-62) after each rendered view, and every densify_interval
+ * iterations densify_and_prune (:513-593): clone, split (N = 2), prune.  Parameters are RAW ([P,1] opacity logits, [P,2] log
+ * scales, [P,4] unnormalised quaternions).  With e = exp(s) and g = accum / denom (a true float32 quotient, NaN -> 0, an
+ * infinity stays), per source row:
+ *   clone:  g >= T and max(e0, e1) <= D: the row is appended unchanged.
+ *   split:  g >= T and max(e0, e1) >  D: the row is REMOVED and leaves two children with the row's opacity, rotation and
+ *           colour, scales = log(e / 1.6), means3D = xyz + R(q) (e0 n0, e1 n1, 0): R is pytorch3d's quaternion_to_matrix of
+ *           the raw quaternion (entries scaled by 2 / |q|^2, q not normalised first), (n0, n1) a standard normal pair per
+ *           child, drawn by the caller.
+ *   prune, of every old row, clone and child: removed when sigmoid(o) < opacity_cull, or (e0 + e1) * 0.5f < scale_cull, or
+ *           world_max > 0 and max(e0, e1) > world_max (for a child with e = exp(log(e_src / 1.6))).  A clone shares its
+ *           source's decision, two siblings share theirs; a split row that is itself too large still leaves its children
+ *           when they pass.
+ * Final row order: [old rows neither split nor pruned] [kept clones] [kept first children] [kept second children], each in
+ * source order.  Old rows keep their Adam moments, every new row gets zero moments.
+ * T = densify_grad_threshold, D = percent_dense * extent, world_max = 0.1 * extent (0 when the configuration's scale_max is
+ * falsy): form the products in double and round each once to float, as torch's scalar comparison does.  T <= 0 is refused:
+ * the reference would then split the clones it has just appended, which no per-row rule reproduces.
+ * The reference's `max_radii2D > scale_max` clause is dead and not implemented: max_radii2D is never updated, and
+ * densification_postfix re-zeroes it before the prune reads it.
+ * Decisions are exact float32 comparisons (see "Exactness" above) of values that contain expf / sigmoid, which no library
+ * rounds correctly: a row within an ulp or two of a prune or size threshold may be decided differently from PyTorch; the
+ * gradient test g >= T is the same correctly rounded quotient everywhere. */
+
+/* Word offsets into the densify workspace after gs2d_map_densify_select (word GS2D_MAP_WS_COUNT: the final row count);
+ * the select call copies the first GS2D_MAP_WS_DENSIFY_WORDS words to `counts` in its one host read. */
+#define GS2D_MAP_WS_DENSIFY_OLD 2       /* old rows kept */
+#define GS2D_MAP_WS_DENSIFY_CLONES 3    /* clones kept */
+#define GS2D_MAP_WS_DENSIFY_CHILDREN 4  /* children kept PER COPY (= split rows whose children survive) */
+#define GS2D_MAP_WS_DENSIFY_N_CLONED 5  /* rows cloned, before the prune */
+#define GS2D_MAP_WS_DENSIFY_N_SPLIT 6   /* rows split, before the prune */
+#define GS2D_MAP_WS_DENSIFY_WORDS 8
+
+/* add_densification_stats: for radii[i] > 0, accum[i] += sqrtf(gx*gx + gy*gy) and denom[i] += 1 with (gx, gy) the first two
+ * of the three floats of row i of dL_dmean2D ([P,3]); other rows are untouched.  radii: [P] int32; accum, denom: [P], updated
+ * in place.  One launch, no host read. */
+int gs2d_map_densify_stats(int P, const int* radii, const float* dL_dmean2D, float* accum, float* denom, void* stream);
+
+/* 0 for P < 0 or P > 2^29 (3 P rows must fit an int). */
+size_t gs2d_map_densify_ws_bytes(int P);
+
+/* Classifies every row, decides the prune of the old row, of its clone and of its children, counts and scans.  Ends with ONE
+ * device-to-host read (32 bytes) and a wait on `stream`; returns the final row count (>= 0).  counts: HOST array of
+ * GS2D_MAP_WS_DENSIFY_WORDS words that receives the workspace header (words not named above are undefined), or NULL. */
+int gs2d_map_densify_select(int P, const float* opacities, const float* scales, const float* accum, const float* denom,
+                            float grad_threshold, float dense_size, float opacity_cull, float scale_cull, float world_max,
+                            void* ws, uint32_t* counts, void* stream);
+
+/* Writes the whole new map in ONE launch from what gs2d_map_densify_select left in `ws` for the same P and arrays.
+ * param_src / param_dst: HOST arrays of 5 device pointers (means3D [.,3], opacities [.,1], scales [.,2], rotations [.,4],
+ * colors [.,3]; P rows in src, the returned row count in dst).  moment_src / moment_dst / moment_widths: HOST arrays of
+ * n_moments <= GS2D_MAP_MAX_ARRAYS entries, 1 <= width <= 4: copied for old rows, zero for new ones.  noise: [P,2,2] float32
+ * (source row, copy, axis) standard normals, read for split rows only.  No destination may overlap a source. */
+int gs2d_map_densify_write(int P, const void* ws, const float* noise, const float* const* param_src, float* const* param_dst,
+                           int n_moments, const float* const* moment_src, float* const* moment_dst, const int* moment_widths,
+                           void* stream);
 
 /* "... src <hash>": the hash of csrc_map/ + this header the library was built from (gaus_slam_amd/build.py). */
 const char* gs2d_map_build_info(void);
