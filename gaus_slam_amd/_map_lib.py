@@ -1,5 +1,5 @@
-"""ctypes binding of the map growth / pruning C ABI (include/gs2d_map.h, libgs2d_map_hip.so).  Like _lib.py it fails loudly
-when the library is missing: there is no CPU fallback."""
+"""ctypes binding of the map growth / pruning C ABI (include/gs2d_map.h) and of the pose optimiser's (include/gs2d_pose.h), both in
+libgs2d_map_hip.so.  Like _lib.py it fails loudly when the library is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -8,10 +8,22 @@ from . import build as _build
 EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_select", "gs2d_map_seed_write",
            "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_densify_stats", "gs2d_map_densify_ws_bytes",
            "gs2d_map_densify_select", "gs2d_map_densify_write", "gs2d_map_build_info", "gs2d_map_last_error"]
+POSE_EXPORTS = ["gs2d_pose_init", "gs2d_pose_step", "gs2d_pose_frame_stats"]  # include/gs2d_pose.h
 MAX_ARRAYS = 16  # GS2D_MAP_MAX_ARRAYS
 WS_COUNT, WS_MEDIAN = 0, 1  # GS2D_MAP_WS_COUNT, GS2D_MAP_WS_MEDIAN: uint32 word offsets into a workspace
 # GS2D_MAP_WS_DENSIFY_*: what gs2d_map_densify_select copies to its `counts` argument
 WS_DENSIFY_OLD, WS_DENSIFY_CLONES, WS_DENSIFY_CHILDREN, WS_DENSIFY_N_CLONED, WS_DENSIFY_N_SPLIT, WS_DENSIFY_WORDS = 2, 3, 4, 5, 6, 8
+
+# GS2D_POSE_*: 32-bit word offsets into a pose state, and the doubles of a gs2d_pose_frame_stats workspace
+POSE_Q, POSE_T, POSE_EXP_AVG, POSE_EXP_AVG_SQ, POSE_STEPS, POSE_CONVERGED_TIMES, POSE_DONE, POSE_STATE_WORDS = 0, 4, 7, 14, 21, 22, 23, 24
+POSE_STATS_WS_DOUBLES = 1536
+
+
+class PoseCfg(C.Structure):
+    """gs2d_pose_cfg, passed by value: index 0 of each pair is the rotation group, index 1 the translation group."""
+    _fields_ = [("lr_init", C.c_double * 2), ("lr_final", C.c_double * 2), ("max_steps", C.c_double * 2), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("converged_th", C.c_double), ("frozen", C.c_int32)]
+
 
 _lib = None
 
@@ -48,6 +60,12 @@ def lib():
     L.gs2d_map_densify_select.argtypes = [i, vp, vp, vp, vp, f, f, f, f, f, vp, C.POINTER(C.c_uint32), vp]
     L.gs2d_map_densify_write.restype = i
     L.gs2d_map_densify_write.argtypes = [i, vp, vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp]
+    L.gs2d_pose_init.restype = i
+    L.gs2d_pose_init.argtypes = [vp, vp, vp, vp, vp]
+    L.gs2d_pose_step.restype = i
+    L.gs2d_pose_step.argtypes = [vp, vp, vp, vp, PoseCfg, vp, vp]
+    L.gs2d_pose_frame_stats.restype = i
+    L.gs2d_pose_frame_stats.argtypes = [i, i, vp, vp, i, f, f, f, f, f, f, vp, vp, vp]
     L.gs2d_map_build_info.restype = C.c_char_p
     L.gs2d_map_last_error.restype = C.c_char_p
     _lib = L

@@ -1,5 +1,6 @@
 """Builds the gfx950 shared libraries with hipcc: the rasterizer library (C ABI in include/gs2d_rasterizer.h) and the map
-growth / pruning library (C ABI in include/gs2d_map.h, sources in csrc_map/).
+growth / pruning library, which also holds the camera pose optimiser (C ABI in include/gs2d_map.h and include/gs2d_pose.h,
+sources in csrc_map/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -23,8 +24,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectoriz
 # profiles were measured on, so code that is not on that path must not move it.
 CSRC_MAP = os.path.join(_HERE, "csrc_map")
 MAP_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_map_hip.so")
-MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip"]
+MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip", "gs2d_pose.hip"]
 MAP_HEADER = os.path.join(_HERE, "..", "include", "gs2d_map.h")
+POSE_HEADER = os.path.join(_HERE, "..", "include", "gs2d_pose.h")
 
 
 def source_hash():
@@ -60,7 +62,8 @@ def _stale():
 
 
 def map_source_hash():
-    """source_hash() of the map library: every file under csrc_map/ plus include/gs2d_map.h (gs2d_map_build_info reports it)."""
+    """source_hash() of the map library: every file under csrc_map/ plus include/gs2d_map.h and include/gs2d_pose.h
+    (gs2d_map_build_info reports it)."""
     import hashlib
     h = hashlib.sha256()
     for f in sorted(os.listdir(CSRC_MAP)):
@@ -69,6 +72,8 @@ def map_source_hash():
             h.update(fh.read())
     with open(MAP_HEADER, "rb") as fh:
         h.update(b"gs2d_map.h\0" + fh.read())
+    with open(POSE_HEADER, "rb") as fh:
+        h.update(b"gs2d_pose.h\0" + fh.read())
     return h.hexdigest()[:16]
 
 
@@ -83,7 +88,7 @@ def _map_stale():
     except OSError:
         return True
     t = os.path.getmtime(MAP_LIB_PATH)
-    deps = [os.path.join(CSRC_MAP, f) for f in os.listdir(CSRC_MAP)] + [MAP_HEADER, os.path.join(CSRC, "gs2d_scan.h"),
+    deps = [os.path.join(CSRC_MAP, f) for f in os.listdir(CSRC_MAP)] + [MAP_HEADER, POSE_HEADER, os.path.join(CSRC, "gs2d_scan.h"),
                                                                         os.path.join(CSRC, "gs2d_common.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
