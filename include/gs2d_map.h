@@ -157,6 +157,39 @@ int gs2d_map_densify_write(int P, const void* ws, const float* noise, const floa
                            int n_moments, const float* const* moment_src, float* const* moment_dst, const int* moment_widths,
                            void* stream);
 
+/* ---- Raw parameters: the mapping iteration as the reference runs it.  It stores opacity logits, log scales and
+ * unnormalised quaternions, activates them on every render (scene/Gaussians.py:299-347, get_render_params) and lets
+ * torch.optim.Adam(eps=1e-15) step the raw values through autograd (Gaussians.py:121-137).  Here that is one launch before the
+ * operator and one after it; the operator itself sees activated values and writes dL/d(activated).  means3D and colours need
+ * no activation: the operator reads them from the raw buffer.  Neither call reads anything back or needs a workspace. */
+
+/* opacities_raw [P,1], scales_raw [P,2], rotations_raw [P,4] -> opacities, scales, rotations of the same shapes, one launch:
+ *   opacities = 1 / (1 + expf(-o));   scales = expf(s);   rotations = q / max(|q|, 1e-12f)   (F.normalize, dim=1, default eps)
+ * with |q| = sqrtf(((q0 q0 + q1 q1) + q2 q2) + q3 q3).  Pointers are 4-byte aligned (they address fields inside
+ * a flat buffer); no output may overlap an input.  P == 0 is a no-op, whatever the pointers; P < 0 or a NULL pointer
+ * returns < 0. */
+int gs2d_map_activate(int P, const float* opacities_raw, const float* scales_raw, const float* rotations_raw, float* opacities,
+                      float* scales, float* rotations, void* stream);
+
+/* Chain rule through the three activations and one Adam step on the raw parameters, one launch.
+ * param_flat, exp_avg, exp_avg_sq (updated in place), grad_flat and raw_grad_out are [13 P] floats in the bucket layout
+ * (field-major: xyz 3P | opacity P | scaling 2P | rotation 4P | rgb 3P); act is the [7 P] block gs2d_map_activate wrote from
+ * THESE parameters (opacities P | scales 2P | rotations 4P); grad_flat holds dL/d(activated), i.e. what the rasterizer's
+ * backward writes when it is fed the activated values.  The raw gradient, per row:
+ *   xyz, rgb:  g
+ *   opacity:   g a (1 - a)                      a from act
+ *   scales:    g e                              e from act
+ *   rotation:  (g - q^ (q^ . g)) / n            n = |q| of the raw quaternion (as above), q^ from act;  when n <= 1e-12f: g / 1e-12f,
+ *                                               which is what autograd's clamp_min gives (its gradient does not reach |q| there)
+ * It then goes through torch.optim.Adam's update (no weight decay, no amsgrad), with the expressions, the double-formed
+ * 1 - beta, bias corrections and lr / (1 - beta1^step) of gs2d_adam_step (gs2d_rasterizer.h): parameters and moments equal
+ * those of gs2d_adam_step on raw_grad_out bit for bit.  group_lr: HOST array of 5 learning rates in field order.
+ * raw_grad_out: receives the raw gradient, or NULL; it may not overlap another argument.  The six buffer bases are 16-byte aligned,
+ * as gs2d_adam_step demands (the fields inside them start at 4-byte aligned offsets for odd P; the kernel uses dword accesses).
+ * P == 0 is a no-op, whatever the pointers; P < 0, step < 1 or a NULL pointer other than raw_grad_out returns < 0. */
+int gs2d_map_raw_step(int P, float* param_flat, const float* act, const float* grad_flat, float* exp_avg, float* exp_avg_sq,
+                      const float* group_lr, double beta1, double beta2, float eps, int step, float* raw_grad_out, void* stream);
+
 /* "... src <hash>": the hash of csrc_map/ + this header the library was built from (gaus_slam_amd/build.py). */
 const char* gs2d_map_build_info(void);
 const char* gs2d_map_last_error(void);
