@@ -8,7 +8,7 @@ from . import build as _build
 EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_select", "gs2d_map_seed_write",
            "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_densify_stats", "gs2d_map_densify_ws_bytes",
            "gs2d_map_densify_select", "gs2d_map_densify_write", "gs2d_map_build_info", "gs2d_map_last_error",
-           "gs2d_map_activate", "gs2d_map_raw_step"]
+           "gs2d_map_activate", "gs2d_map_raw_step", "gs2d_map_merge"]
 POSE_EXPORTS = ["gs2d_pose_init", "gs2d_pose_step", "gs2d_pose_frame_stats"]  # include/gs2d_pose.h
 MAX_ARRAYS = 16  # GS2D_MAP_MAX_ARRAYS
 WS_COUNT, WS_MEDIAN = 0, 1  # GS2D_MAP_WS_COUNT, GS2D_MAP_WS_MEDIAN: uint32 word offsets into a workspace
@@ -65,6 +65,8 @@ def lib():
     L.gs2d_map_activate.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
     L.gs2d_map_raw_step.restype = i
     L.gs2d_map_raw_step.argtypes = [i, vp, vp, vp, vp, vp, C.POINTER(f), C.c_double, C.c_double, f, i, vp, vp]
+    L.gs2d_map_merge.restype = i
+    L.gs2d_map_merge.argtypes = [i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp, f, vp]
     L.gs2d_pose_init.restype = i
     L.gs2d_pose_init.argtypes = [vp, vp, vp, vp, vp]
     L.gs2d_pose_step.restype = i

@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectoriz
 # profiles were measured on, so code that is not on that path must not move it.
 CSRC_MAP = os.path.join(_HERE, "csrc_map")
 MAP_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_map_hip.so")
-MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip", "gs2d_pose.hip", "gs2d_map_raw.hip"]
+MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip", "gs2d_pose.hip", "gs2d_map_raw.hip", "gs2d_map_merge.hip"]
 MAP_HEADER = os.path.join(_HERE, "..", "include", "gs2d_map.h")
 POSE_HEADER = os.path.join(_HERE, "..", "include", "gs2d_pose.h")
 

@@ -9,6 +9,7 @@
 // Kernel plan (wave64, 256 threads, 1024 items per workgroup everywhere):
 //   seed_select, mode 0: err + 1st histogram | 2nd | 3rd | 4th histogram | flags + block counts | scan of block counts
 //   seed_select, mode 1:                                                  flags + block counts | scan of block counts
+//   seed_select, mode 2:                                                  the same two; allmap is never read
 //   seed_write:          one kernel (block-local scan of the flags + the scanned block counts -> row, then the seed)
 //   prune_select:        flags + block counts | scan of block counts
 //   compact:             one kernel for all arrays (block-local list of kept rows in LDS, coalesced stores per array)
@@ -155,10 +156,10 @@ seed_hist_kernel(int pass, int N, uint32_t rank, const uint32_t* __restrict__ er
 
 struct SelectCfg { int mode, W, H; float sil, edge; DepthCfg dc; };
 
-// source depth of pixel i: gt (mode 0) or the rendered depth (mode 1)
+// source depth of pixel i: gt (modes 0 and 2) or the rendered depth (mode 1)
 __device__ __forceinline__ float source_depth(const SelectCfg& c, int N, int i, const float* __restrict__ allmap, const float* __restrict__ gt)
 {
-    return c.mode == 0 ? gt[i] : rendered_depth(c.dc, allmap[i], allmap[(size_t)N + i]);
+    return c.mode != GS2D_MAP_MODE_EDGE ? gt[i] : rendered_depth(c.dc, allmap[i], allmap[(size_t)N + i]);
 }
 
 // get_normalmask_from_depth (common_utils.py:87-103): its four aliased in-place statements amount to a 3x3 erosion of
@@ -192,14 +193,16 @@ seed_flag_kernel(SelectCfg c, int N, uint32_t rank, const float* __restrict__ al
     for (int j = 0; j < 4; j++) {
         const int i = i0 + j;
         if (i >= N) break;
-        const float A = allmap[(size_t)N + i], g = gt[i];
-        bool add;
-        if (c.mode == 0) {
-            const float d = rendered_depth(c.dc, allmap[i], A);
-            add = (A < c.sil) || ((d > g) && (__uint_as_float(zbuf[i]) > thr));
-        } else {
-            add = (A > c.edge) && (A < c.sil) && (g < 0.001f);
-            zbuf[i] = __float_as_uint(rendered_depth(c.dc, allmap[i], A));  // seed_write's z
+        bool add = true;  // mode 2: every pixel, the validity mask alone decides (allmap may be NULL)
+        if (c.mode != GS2D_MAP_MODE_ALL) {
+            const float A = allmap[(size_t)N + i], g = gt[i];
+            if (c.mode == 0) {
+                const float d = rendered_depth(c.dc, allmap[i], A);
+                add = (A < c.sil) || ((d > g) && (__uint_as_float(zbuf[i]) > thr));
+            } else {
+                add = (A > c.edge) && (A < c.sil) && (g < 0.001f);
+                zbuf[i] = __float_as_uint(rendered_depth(c.dc, allmap[i], A));  // seed_write's z
+            }
         }
         if (add) add = valid3x3(c, N, i % c.W, i / c.W, allmap, gt);
         flags[i] = add ? 1 : 0;
@@ -432,9 +435,10 @@ int gs2d_map_seed_select(int mode, int width, int height, const float* allmap, c
                          float edge_thres, int use_weight_norm, float eps, float depth_near, float depth_far, void* ws,
                          void* stream)
 {
-    if (mode != GS2D_MAP_MODE_SPLATAM && mode != GS2D_MAP_MODE_EDGE) return fail("gs2d_map_seed_select: mode must be 0 (splatam) or 1 (edge growth)");
+    if (mode != GS2D_MAP_MODE_SPLATAM && mode != GS2D_MAP_MODE_EDGE && mode != GS2D_MAP_MODE_ALL)
+        return fail("gs2d_map_seed_select: mode must be 0 (splatam), 1 (edge growth) or 2 (all)");
     if (bad_size(width, height)) return fail("gs2d_map_seed_select: width and height must be >= 1 and width*height <= 2^30");
-    if (!allmap || !gt_depth || !ws) return fail("gs2d_map_seed_select: NULL pointer");
+    if ((!allmap && mode != GS2D_MAP_MODE_ALL) || !gt_depth || !ws) return fail("gs2d_map_seed_select: NULL pointer");
     if (((uintptr_t)ws | (uintptr_t)allmap | (uintptr_t)gt_depth) & 3) return fail("gs2d_map_seed_select: misaligned pointer");
     hipStream_t s = (hipStream_t)stream;
     const SeedLayout L = seed_layout(width, height);
@@ -466,16 +470,17 @@ int gs2d_map_seed_write(int mode, int width, int height, const float* allmap, co
                         float fx, float fy, float cx, float cy, const float* c2w, int activated, const void* ws, float* means3D,
                         float* opacities, float* scales, float* rotations, float* colors, int* pixel_index, void* stream)
 {
-    if (mode != GS2D_MAP_MODE_SPLATAM && mode != GS2D_MAP_MODE_EDGE) return fail("gs2d_map_seed_write: mode must be 0 (splatam) or 1 (edge growth)");
+    if (mode != GS2D_MAP_MODE_SPLATAM && mode != GS2D_MAP_MODE_EDGE && mode != GS2D_MAP_MODE_ALL)
+        return fail("gs2d_map_seed_write: mode must be 0 (splatam), 1 (edge growth) or 2 (all)");
     if (bad_size(width, height)) return fail("gs2d_map_seed_write: width and height must be >= 1 and width*height <= 2^30");
-    if (!allmap || !gt_color_hwc || !gt_depth || !c2w || !ws || !means3D || !opacities || !scales || !rotations || !colors)
+    if ((!allmap && mode != GS2D_MAP_MODE_ALL) || !gt_color_hwc || !gt_depth || !c2w || !ws || !means3D || !opacities || !scales || !rotations || !colors)
         return fail("gs2d_map_seed_write: NULL pointer");
     if (((uintptr_t)ws | (uintptr_t)gt_color_hwc | (uintptr_t)gt_depth | (uintptr_t)c2w | (uintptr_t)means3D | (uintptr_t)opacities |
          (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)colors | (uintptr_t)pixel_index) & 3)
         return fail("gs2d_map_seed_write: misaligned pointer");
     const SeedLayout L = seed_layout(width, height);
     const char* w = (const char*)ws;
-    const float* zsrc = mode == GS2D_MAP_MODE_SPLATAM ? gt_depth : (const float*)(w + L.zbuf);
+    const float* zsrc = mode == GS2D_MAP_MODE_EDGE ? (const float*)(w + L.zbuf) : gt_depth;
     const SeedOut o{means3D, opacities, scales, rotations, colors, pixel_index};
     hipLaunchKernelGGL(seed_write_kernel, dim3((unsigned)L.nblk), dim3(256), 0, (hipStream_t)stream, mode, width, height,
                        Cam{fx, fy, cx, cy}, c2w, activated != 0, zsrc, gt_color_hwc, (const uint8_t*)(w + L.flags),

@@ -32,7 +32,7 @@ from .ba_shard import BUCKET_FIELDS, BUCKET_FLOATS
 from .optim import _views
 from .rasterizer import _on_device, _stream_ptr
 
-MODES = {"splatam": 0, "edge": 1}
+MODES = {"splatam": 0, "edge": 1, "all": 2}  # GS2D_MAP_MODE_*
 
 # What seed_select leaves behind for seed_write: the seed count, the opaque device workspace and what it was computed for.
 SeedSelection = namedtuple("SeedSelection", "n ws mode width height")
@@ -53,20 +53,28 @@ def _check_tensor(t, name, shape=None, numel=None):
     _require(t.is_contiguous(), f"{name} must be contiguous")
 
 
-def _check_frame(allmap, gt_color, gt_depth, device=True):
-    _require(isinstance(allmap, torch.Tensor) and allmap.dim() == 3 and allmap.shape[0] == 7,
-             "allmap must be the [7,H,W] rasterizer output")
-    H, W = int(allmap.shape[1]), int(allmap.shape[2])
-    _require(H >= 1 and W >= 1 and H * W <= 1 << 30, "allmap must have 1 <= H*W <= 2^30 pixels")
-    _check_tensor(allmap, "allmap")
+def _check_frame(allmap, gt_color, gt_depth, device=True, no_allmap=False):
+    """Shapes, dtypes and (device=True) devices of one frame; returns (W, H).  no_allmap: allmap may be None (mode "all", which
+    never reads it); the size is then gt_depth's."""
+    if allmap is None and no_allmap:
+        _require(isinstance(gt_depth, torch.Tensor) and gt_depth.dim() in (2, 3), "gt_depth must be [H,W] or [H,W,1]")
+        H, W = int(gt_depth.shape[0]), int(gt_depth.shape[1])
+        _require(H >= 1 and W >= 1 and H * W <= 1 << 30, "gt_depth must have 1 <= H*W <= 2^30 pixels")
+    else:
+        _require(isinstance(allmap, torch.Tensor) and allmap.dim() == 3 and allmap.shape[0] == 7,
+                 "allmap must be the [7,H,W] rasterizer output")
+        H, W = int(allmap.shape[1]), int(allmap.shape[2])
+        _require(H >= 1 and W >= 1 and H * W <= 1 << 30, "allmap must have 1 <= H*W <= 2^30 pixels")
+        _check_tensor(allmap, "allmap")
     if gt_color is not None:
         _check_tensor(gt_color, "gt_color", shape=(H, W, 3))
     _check_tensor(gt_depth, "gt_depth", numel=H * W)
     _require(gt_depth.dim() >= 2 and tuple(gt_depth.shape[:2]) == (H, W), f"gt_depth must be [H,W] or [H,W,1] = [{H},{W}]")
+    dev = gt_depth.device if allmap is None else allmap.device
     for t, name in ((allmap, "allmap"), (gt_color, "gt_color"), (gt_depth, "gt_depth")):
         if device and t is not None:
             _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
-            _require(t.device == allmap.device, f"{name} must be on {allmap.device}")
+            _require(t.device == dev, f"{name} must be on {dev}")
     return W, H
 
 
@@ -86,18 +94,26 @@ def c2w_from_w2c(w2c):
     return torch.linalg.inv(w2c.detach().float()).contiguous()
 
 
-def seed_select(allmap, gt_depth, *, mode="splatam", sil_thres, edge_thres=0.4, use_weight_norm=True, eps=1e-6, depth_near=1e-2,
-                depth_far=1e2):
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def seed_select(allmap, gt_depth, *, mode="splatam", sil_thres=None, edge_thres=0.4, use_weight_norm=True, eps=1e-6,
+                depth_near=1e-2, depth_far=1e2):
     """Which pixels seed a Gaussian (gs2d_map_seed_select).  Returns a SeedSelection; `.n` is the seed count (one host read).
     mode "splatam": Densify.py:16-19 (silhouette below sil_thres, or the render behind gt by more than 50 medians of the depth
-    error); mode "edge": Densify.py:29-31.  Both are ANDed with the validity mask of get_pointcloud."""
+    error); mode "edge": Densify.py:29-31; mode "all": every pixel (Frontend.create_map) -- allmap may then be None, and the
+    thresholds and the depth configuration are not read.  Each is ANDed with the validity mask of get_pointcloud."""
     _require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
-    W, H = _check_frame(allmap, None, gt_depth)
-    dev = allmap.device
+    if mode == "all":
+        sil_thres = 0.0
+    _require(sil_thres is not None, f"mode {mode!r} needs sil_thres")
+    W, H = _check_frame(allmap, None, gt_depth, no_allmap=mode == "all")
+    dev = gt_depth.device
     L = _map_lib.lib()
     ws = torch.empty(L.gs2d_map_seed_ws_bytes(W, H), dtype=torch.uint8, device=dev)
     with _on_device(dev):
-        n = L.gs2d_map_seed_select(MODES[mode], W, H, allmap.data_ptr(), gt_depth.data_ptr(), float(sil_thres), float(edge_thres),
+        n = L.gs2d_map_seed_select(MODES[mode], W, H, _ptr(allmap), gt_depth.data_ptr(), float(sil_thres), float(edge_thres),
                                    int(bool(use_weight_norm)), float(eps), float(depth_near), float(depth_far), ws.data_ptr(),
                                    _stream_ptr(dev))
     if n < 0:
@@ -116,9 +132,9 @@ def seed_median(sel):
 def seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pixel_index=None, activated=False):
     """Writes the seeds of `sel` into `out`, a dict of BUCKET_FIELDS names to contiguous float32 [n,k] tensors (e.g. the tails
     of a re-allocated SoA); pixel_index: int32 [n] or None (gs2d_map_seed_write)."""
-    W, H = _check_frame(allmap, gt_color, gt_depth)
+    W, H = _check_frame(allmap, gt_color, gt_depth, no_allmap=sel.mode == "all")
     _require((W, H) == (sel.width, sel.height), "the selection was computed for another image size")
-    dev = allmap.device
+    dev = gt_depth.device
     for name, k in BUCKET_FIELDS.items():
         _check_tensor(out[name], f"out[{name!r}]", shape=(sel.n, k))
         _require(out[name].device == dev, f"out[{name!r}] must be on {dev}")
@@ -132,7 +148,7 @@ def seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pixel_inde
         return
     with _on_device(dev):
         rc = _map_lib.lib().gs2d_map_seed_write(
-            MODES[sel.mode], W, H, allmap.data_ptr(), gt_color.data_ptr(), gt_depth.data_ptr(), fx, fy, cx, cy, c2w.data_ptr(),
+            MODES[sel.mode], W, H, _ptr(allmap), gt_color.data_ptr(), gt_depth.data_ptr(), fx, fy, cx, cy, c2w.data_ptr(),
             int(bool(activated)), sel.ws.data_ptr(), out["means3D"].data_ptr(), out["opacities"].data_ptr(),
             out["scales"].data_ptr(), out["rotations"].data_ptr(), out["colors"].data_ptr(),
             None if pixel_index is None else pixel_index.data_ptr(), _stream_ptr(dev))
@@ -140,23 +156,28 @@ def seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pixel_inde
         raise RuntimeError(_map_lib.last_error())
 
 
-def seed_from_frame(allmap, gt_color, gt_depth, intrinsics, w2c, *, mode="splatam", sil_thres, edge_thres=0.4,
-                    use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2, activated=False):
+def seed_from_frame(allmap, gt_color, gt_depth, intrinsics, w2c, *, mode="splatam", sil_thres=None, edge_thres=0.4,
+                    use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2, activated=False, c2w=None):
     """New Gaussians from one rendered view and its RGB-D frame: the add mask of Densify.py, get_pointcloud and the
     initialisation of add_gaussians_from_pcd.
 
     allmap: raw [7,H,W] rasterizer output; gt_color: [H,W,3]; gt_depth: [H,W] (or [H,W,1]); intrinsics: [3,3]; w2c: [4,4].
     Returns an OrderedDict with the BUCKET_FIELDS names (means3D [n,3], opacities [n,1], scales [n,2], rotations [n,4],
     colors [n,3]; raw values, or activated ones with activated=True) plus `pixel_index` (int32 [n], y*W + x), seeds in row-major
-    pixel order.  The `sample_num` subsampling of get_pointcloud is not offered (see the module docstring)."""
+    pixel order.  The `sample_num` subsampling of get_pointcloud is not offered (see the module docstring).
+    mode "all" (every valid pixel, Frontend.create_map) accepts allmap=None and needs no sil_thres.  c2w: the float32 [4,4]
+    camera-to-world matrix on the device when the caller has it already; w2c is then not read."""
     _require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
-    _check_frame(allmap, gt_color, gt_depth, device=False)  # shapes and dtypes first, devices second
+    _require(mode == "all" or sil_thres is not None, f"mode {mode!r} needs sil_thres")
+    no_allmap = mode == "all"
+    _check_frame(allmap, gt_color, gt_depth, device=False, no_allmap=no_allmap)  # shapes and dtypes first, devices second
     _intrinsics(intrinsics)
-    _check_frame(allmap, gt_color, gt_depth)
-    c2w = c2w_from_w2c(w2c)
+    _check_frame(allmap, gt_color, gt_depth, no_allmap=no_allmap)
+    if c2w is None:
+        c2w = c2w_from_w2c(w2c)
     sel = seed_select(allmap, gt_depth, mode=mode, sil_thres=sil_thres, edge_thres=edge_thres, use_weight_norm=use_weight_norm,
                       eps=eps, depth_near=depth_near, depth_far=depth_far)
-    dev = allmap.device
+    dev = gt_depth.device
     out = OrderedDict((name, torch.empty((sel.n, k), dtype=torch.float32, device=dev)) for name, k in BUCKET_FIELDS.items())
     pix = torch.empty(sel.n, dtype=torch.int32, device=dev)
     seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pix, activated)

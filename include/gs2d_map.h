@@ -14,6 +14,13 @@
  * and the step its backend runs inside every mapping / bundle-adjustment iteration (scene/Gaussians.py:58-62,513-593:
  * add_densification_stats, densify_and_prune), as gs2d_map_densify_stats / _select / _write, described further down.
  *
+ * The two steps that join local maps into the global one are here as well:
+ *
+ *   mode GS2D_MAP_MODE_ALL of gs2d_map_seed_select / _write <- slam/Frontend.py:63-73 (create_map: get_pointcloud of a whole
+ *                            frame, then create_from_pcd), without a rendered view and without a median
+ *   gs2d_map_merge        <- slam/Backend.py:158-161,225-227 (transfer_map_params, the opacity clamp) and
+ *                            scene/Gaussians.py:378 (add_params: parameters AND both Adam moments), in one launch
+ *
  * Conventions follow gs2d_rasterizer.h: device pointers to float32 / int32 data in plain C layouts, `stream` is a
  * hipStream_t (NULL = the null stream), a return value < 0 signals an error that gs2d_map_last_error() describes, and no
  * torch type appears here.  Workspaces are allocated by the caller (4-byte aligned at least, any content) and sized by
@@ -27,6 +34,15 @@
  * are equal to the reference's bit for bit.  Seed VALUES are another float32 evaluation of the same formulas, except the
  * normal: the neighbour points, their two differences and the cross product are evaluated in float64 on the float32 inputs
  * (the differences cancel most of the points' leading bits), the frame and the quaternion in float32 again.
+ * Mode GS2D_MAP_MODE_ALL selects by the validity mask alone, which is two float32 comparisons per pixel: its seed list is
+ * that of get_pointcloud bit for bit, and its seed values are those mode 0 writes for the same pixels.
+ * gs2d_map_merge copies bits (old rows, scales, colours, the opacity that wins the comparison with the cap) and writes exact
+ * zeros.  Its means are the float32 expression ((r0 x + r1 y) + r2 z) + t as written, so they differ from a float64
+ * evaluation by the rounding of those six operations and equal the input under the identity transfer.  Its rotations are
+ * evaluated in float64 on the float32 inputs -- R(q), the product with the transfer's rotation, matrix_to_quaternion -- then
+ * normalised and rounded once: they deviate from the float64 reference by the final rounding, plus, on a transfer whose
+ * rotation block is not exactly orthonormal, by the normalisation (the reference's result is then not a unit quaternion; the
+ * difference is below max|R_t R_t^T - I|).  The sign is matrix_to_quaternion's (real part >= 0).
  *
  * Out of contract: non-finite gt_depth (the reference multiplies a mask by |d - gt|, which turns an infinity into NaN and
  * poisons its median).  Non-finite rasterizer output is handled as nan_to_num(., 0, 0) handles it.
@@ -53,6 +69,7 @@ extern "C" {
 
 #define GS2D_MAP_MODE_SPLATAM 0
 #define GS2D_MAP_MODE_EDGE 1
+#define GS2D_MAP_MODE_ALL 2
 
 size_t gs2d_map_seed_ws_bytes(int width, int height);
 size_t gs2d_map_prune_ws_bytes(int P);
@@ -64,7 +81,9 @@ size_t gs2d_map_prune_ws_bytes(int P);
  *   mode 0 ("splatam"):     err = gt > 0 ? |d - gt| : 0;  med = element of rank (HW-1)/2 of sorted err (torch.median);
  *                           add = (A < sil_thres) | ((d > gt) & (err > 50 med));  source depth z = gt
  *   mode 1 ("edge growth"): add = (A > edge_thres) & (A < sil_thres) & (gt < 0.001);  z = d
- * Either is ANDed with the validity mask 0.01 < z < 15 at the pixel and at each of its in-image 3x3 neighbours.
+ *   mode 2 ("all"):         add = 1;  z = gt.  allmap may be NULL, no median is computed, and sil_thres, edge_thres,
+ *                           use_weight_norm, eps, depth_near and depth_far are ignored (Frontend.create_map: the whole frame)
+ * Each is ANDed with the validity mask 0.01 < z < 15 at the pixel and at each of its in-image 3x3 neighbours.
  * Returns the number of seeds (>= 0). */
 int gs2d_map_seed_select(int mode, int width, int height, const float* allmap, const float* gt_depth, float sil_thres,
                          float edge_thres, int use_weight_norm, float eps, float depth_near, float depth_far, void* ws,
@@ -81,7 +100,8 @@ int gs2d_map_seed_select(int mode, int width, int height, const float* allmap, c
  *               n = normalize(cross(P[y+1,x] - P[y-1,x], P[y,x+1] - P[y,x-1])) over the WORLD points of the four neighbours,
  *               up = (ny nz, nx nz, -2 nx ny), then nan_to_num(., 0, 0) and (1,0,0,0) when the norm is < 1e-3 (a normal along
  *               a coordinate axis: up = 0); (1,0,0,0) on the image border (see "departures" above).
- * Mode 1 reads its source depth z = d from `ws`, where the select call left it. */
+ * Mode 1 reads its source depth z = d from `ws`, where the select call left it.  Mode 2 writes what mode 0 writes (allmap may
+ * be NULL). */
 int gs2d_map_seed_write(int mode, int width, int height, const float* allmap, const float* gt_color_hwc, const float* gt_depth,
                         float fx, float fy, float cx, float cy, const float* c2w, int activated, const void* ws, float* means3D,
                         float* opacities, float* scales, float* rotations, float* colors, int* pixel_index, void* stream);
@@ -156,6 +176,31 @@ int gs2d_map_densify_select(int P, const float* opacities, const float* scales, 
 int gs2d_map_densify_write(int P, const void* ws, const float* noise, const float* const* param_src, float* const* param_dst,
                            int n_moments, const float* const* moment_src, float* const* moment_dst, const int* moment_widths,
                            void* stream);
+
+/* ---- Handing a local map to the global map (slam/Backend.py:225-227): rigid transfer of the incoming rows, the opacity
+ * clamp, and the concatenation of parameters and Adam moments, written ONCE into re-allocated arrays.  One launch, no
+ * workspace, no host read, nothing synchronises.
+ * param_src: HOST array of 5 device pointers, P rows (means3D [.,3], opacities [.,1], scales [.,2], rotations [.,4], colors
+ * [.,3]); incoming: the same five fields, n rows, the local map's RAW parameters; param_dst: the same five, P + n rows.
+ * moment_src / moment_dst / moment_widths: HOST arrays of n_moments <= GS2D_MAP_MAX_ARRAYS entries, 1 <= width <= 4, as for
+ * gs2d_map_densify_write.  transfer: 16 floats, row-major [R_t | t], ON THE DEVICE (the caller forms inv(lm_w2c) @ ref2f0
+ * there).  opacity_cap is compared with the stored value; +INFINITY = no cap.
+ * Rows [0,P) of every destination (parameters and moments) are bit copies of the source; rows [P,P+n) of every moment array
+ * are zero.  Incoming row i becomes row P + i:
+ *   means3D   = ((r0 x + r1 y) + r2 z) + t per component, float32, in that order
+ *   opacities = o < cap ? o : cap   (one of the two inputs, bit for bit)
+ *   scales, colors: bit copies
+ *   rotations = a unit quaternion of R_t R(q), R(q) pytorch3d's quaternion_to_matrix of the RAW quaternion (entries scaled by
+ *               2 / |q|^2: q need not be normalised) -- build_quaternion(transfer[:3,:3] @ build_rotation(q)) up to float32
+ *               rounding and normalisation, real part >= 0 (see "Exactness")
+ * P == 0 (create_params with a transform) and n == 0 (a copy) are valid; pointers the sizes do not need may be NULL.
+ * P < 0, n < 0, P + n > 2^29, a width outside [1,4], a NaN cap, or a NULL / misaligned pointer the sizes require returns < 0.
+ * Every array is 4-byte aligned at least (fields of flat [13 rows] buffers are no more than that for odd row counts); the
+ * kernel widens an access only where both sides are 16-byte aligned.  No destination may overlap a source.
+ * Out of contract: non-finite inputs and |q| = 0 (the reference yields NaN there, and so does this). */
+int gs2d_map_merge(int P, int n, const float* const* param_src, const float* const* incoming, float* const* param_dst,
+                   int n_moments, const float* const* moment_src, float* const* moment_dst, const int* moment_widths,
+                   const float* transfer, float opacity_cap, void* stream);
 
 /* ---- Raw parameters: the mapping iteration as the reference runs it.  It stores opacity logits, log scales and
  * unnormalised quaternions, activates them on every render (scene/Gaussians.py:299-347, get_render_params) and lets
