@@ -4,6 +4,7 @@ import ctypes as C
 import os
 
 from . import build as _build
+from .rasterizer import _on_device, _stream_ptr
 
 EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_select", "gs2d_map_seed_write",
            "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_densify_stats", "gs2d_map_densify_ws_bytes",
@@ -81,6 +82,16 @@ def lib():
 
 def last_error():
     return lib().gs2d_map_last_error().decode()
+
+
+def call(name, device, *args):
+    """Entry point `name` of the library with `args` and, as its last argument, torch's current stream on `device`, with that
+    device current.  Returns what it returns (a count, or 0); a negative return raises RuntimeError with the library's text."""
+    with _on_device(device):
+        rc = getattr(lib(), name)(*args, _stream_ptr(device))
+    if rc < 0:
+        raise RuntimeError(last_error())
+    return rc
 
 
 def build_info():

@@ -27,85 +27,77 @@ MAP_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_map_hip.so")
 MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip", "gs2d_pose.hip", "gs2d_map_raw.hip", "gs2d_map_merge.hip"]
 MAP_HEADER = os.path.join(_HERE, "..", "include", "gs2d_map.h")
 POSE_HEADER = os.path.join(_HERE, "..", "include", "gs2d_pose.h")
+RASTERIZER_HEADER = os.path.join(_HERE, "..", "include", "gs2d_rasterizer.h")
+
+
+def _hash(directory, headers):
+    """sha256 (first 16 hex digits) over every file of `directory` in name order, then `headers` in the order given: name, a
+    zero byte, content."""
+    import hashlib
+    h = hashlib.sha256()
+    for path in [os.path.join(directory, f) for f in sorted(os.listdir(directory))] + list(headers):
+        with open(path, "rb") as fh:
+            h.update(os.path.basename(path).encode() + b"\0" + fh.read())
+    return h.hexdigest()[:16]
+
+
+def _is_stale(lib_path, source_hash, deps):
+    """No library, no or another hash in its `.hash` sidecar (written by _compile), or a dependency newer than the library."""
+    if not os.path.exists(lib_path):
+        return True
+    try:
+        with open(lib_path + ".hash") as fh:
+            if fh.read().strip() != source_hash:
+                return True
+    except OSError:
+        return True
+    t = os.path.getmtime(lib_path)
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def _compile(lib_path, sources, hash_macro, source_hash, verbose):
+    """One hipcc call with FLAGS and the hash as `hash_macro`, then the `.hash` sidecar _is_stale reads.  Returns lib_path."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc] + FLAGS + [f'-D{hash_macro}="{source_hash}"', "-o", lib_path] + sources
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    with open(lib_path + ".hash", "w") as fh:
+        fh.write(source_hash + "\n")
+    return lib_path
 
 
 def source_hash():
-    """sha256 (first 16 hex digits) over the kernel sources the library is built from: every file under csrc/ plus the C-ABI
-    header, in name order (name and content).  Compiled into the library (gs2d_build_info) and written into every JSON bench.py
-    emits, so that a kept artifact says which kernels produced it (tests/test_host.py checks the profiles of the current round)."""
-    import hashlib
-    h = hashlib.sha256()
-    files = sorted(os.listdir(CSRC))
-    for f in files:
-        h.update(f.encode() + b"\0")
-        with open(os.path.join(CSRC, f), "rb") as fh:
-            h.update(fh.read())
-    with open(os.path.join(_HERE, "..", "include", "gs2d_rasterizer.h"), "rb") as fh:
-        h.update(b"gs2d_rasterizer.h\0" + fh.read())
-    return h.hexdigest()[:16]
+    """Hash of the kernel sources the library is built from: every file under csrc/ plus the C-ABI header (_hash).  Compiled
+    into the library (gs2d_build_info) and written into every JSON bench.py emits, so that a kept artifact says which kernels
+    produced it (tests/test_host.py checks the profiles of the current round)."""
+    return _hash(CSRC, [RASTERIZER_HEADER])
 
 
 def _stale():
     if os.environ.get("GS2D_LIB_PATH"):
         return False
-    if not os.path.exists(LIB_PATH):
-        return True
-    try:  # the hash the library was built from (sidecar written by build())
-        with open(LIB_PATH + ".hash") as fh:
-            if fh.read().strip() != source_hash():
-                return True
-    except OSError:
-        return True
-    t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", "gs2d_rasterizer.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return _is_stale(LIB_PATH, source_hash(), [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [RASTERIZER_HEADER])
 
 
 def map_source_hash():
     """source_hash() of the map library: every file under csrc_map/ plus include/gs2d_map.h and include/gs2d_pose.h
     (gs2d_map_build_info reports it)."""
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(CSRC_MAP)):
-        h.update(f.encode() + b"\0")
-        with open(os.path.join(CSRC_MAP, f), "rb") as fh:
-            h.update(fh.read())
-    with open(MAP_HEADER, "rb") as fh:
-        h.update(b"gs2d_map.h\0" + fh.read())
-    with open(POSE_HEADER, "rb") as fh:
-        h.update(b"gs2d_pose.h\0" + fh.read())
-    return h.hexdigest()[:16]
+    return _hash(CSRC_MAP, [MAP_HEADER, POSE_HEADER])
 
 
 def _map_stale():
     """The map library includes ../csrc/gs2d_scan.h and gs2d_common.h: newer copies of those make it stale as well."""
-    if not os.path.exists(MAP_LIB_PATH):
-        return True
-    try:
-        with open(MAP_LIB_PATH + ".hash") as fh:
-            if fh.read().strip() != map_source_hash():
-                return True
-    except OSError:
-        return True
-    t = os.path.getmtime(MAP_LIB_PATH)
     deps = [os.path.join(CSRC_MAP, f) for f in os.listdir(CSRC_MAP)] + [MAP_HEADER, POSE_HEADER, os.path.join(CSRC, "gs2d_scan.h"),
                                                                         os.path.join(CSRC, "gs2d_common.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return _is_stale(MAP_LIB_PATH, map_source_hash(), deps)
 
 
 def build_map(force=False, verbose=False):
     if not force and not _map_stale():
         return MAP_LIB_PATH
-    os.makedirs(LIB_DIR, exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    sh = map_source_hash()
-    cmd = [hipcc] + FLAGS + [f'-DGS2D_MAP_SOURCE_HASH="{sh}"', "-o", MAP_LIB_PATH] + [os.path.join(CSRC_MAP, f) for f in MAP_SOURCES]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    with open(MAP_LIB_PATH + ".hash", "w") as fh:
-        fh.write(sh + "\n")
-    return MAP_LIB_PATH
+    return _compile(MAP_LIB_PATH, [os.path.join(CSRC_MAP, f) for f in MAP_SOURCES], "GS2D_MAP_SOURCE_HASH", map_source_hash(), verbose)
 
 
 def build(force=False, verbose=False):
@@ -113,17 +105,8 @@ def build(force=False, verbose=False):
     build_map(force, verbose)
     if not force and not _stale():
         return LIB_PATH
-    os.makedirs(LIB_DIR, exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
-    sh = source_hash()
-    cmd = [hipcc] + FLAGS + [f'-DGS2D_SOURCE_HASH="{sh}"', "-o", LIB_PATH] + srcs
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    with open(LIB_PATH + ".hash", "w") as fh:
-        fh.write(sh + "\n")
-    return LIB_PATH
+    return _compile(LIB_PATH, srcs, "GS2D_SOURCE_HASH", source_hash(), verbose)
 
 
 if __name__ == "__main__":

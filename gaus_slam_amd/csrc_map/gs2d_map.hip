@@ -20,49 +20,29 @@
 // from the 256 global counters (a 256-wide scan), which is cheaper than a dependent single-workgroup launch.  Atomics feed
 // the histograms only; the order of seeds and of kept rows comes from scans.
 #include "../csrc/gs2d_scan.h"
-#include "../../include/gs2d_map.h"
+#include "gs2d_map_internal.h"
 #include <float.h>
-#include <math.h>
-#include <stdio.h>
+
+static thread_local char g_err[256] = "";
+int gs2d_map_fail(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); return -1; }
+int gs2d_map_fail_hip(const char* what, hipError_t e) { snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e)); return -1; }
 
 namespace {
 
-constexpr int ITEMS = GS2D_SCAN_ITEMS;  // 1024 = 256 threads x 4
-constexpr size_t HDR_BYTES = 256;
 constexpr size_t HIST_BYTES = 4 * 256 * sizeof(uint32_t);
 
-thread_local char g_err[256] = "";
-int fail(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); return -1; }
-int fail_hip(const char* what, hipError_t e) { snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e)); return -1; }
-
-struct SeedLayout { size_t hist, zbuf, flags, block_sums, total; int nblk; };
+// header | four digit histograms | one word per pixel | the flags and block counts of the pixels
+struct SeedLayout { size_t hist, zbuf; RowLayout rows; };
 SeedLayout seed_layout(int W, int H)
 {
     SeedLayout L;
     const size_t n = (size_t)W * H;
-    L.nblk = (int)((n + ITEMS - 1) / ITEMS);
-    size_t o = HDR_BYTES;
-    L.hist = o; o += HIST_BYTES;
-    L.zbuf = o; o = gs2d_align_up(o + 4 * n, 256);   // mode 0: bit patterns of err; mode 1: the rendered depth d
-    L.flags = o; o = gs2d_align_up(o + n, 256);
-    L.block_sums = o; o = gs2d_align_up(o + 4 * ((size_t)L.nblk + 64), 256);
-    L.total = o;
+    L.hist = HDR_BYTES;
+    L.zbuf = L.hist + HIST_BYTES;  // mode 0: bit patterns of err; mode 1: the rendered depth d
+    L.rows = row_layout(n, 1, gs2d_align_up(L.zbuf + 4 * n, 256));
     return L;
 }
-struct PruneLayout { size_t flags, block_sums, total; int nblk; };
-PruneLayout prune_layout(int P)
-{
-    PruneLayout L;
-    const size_t n = (size_t)(P > 0 ? P : 1);
-    L.nblk = (int)((n + ITEMS - 1) / ITEMS);
-    size_t o = HDR_BYTES;
-    L.flags = o; o = gs2d_align_up(o + n, 256);
-    L.block_sums = o; o = gs2d_align_up(o + 4 * ((size_t)L.nblk + 64), 256);
-    L.total = o;
-    return L;
-}
-
-struct DepthCfg { int use_weight_norm; float eps, near, far; };
+RowLayout prune_layout(int P) { return row_layout((size_t)(P > 0 ? P : 1), 1); }
 
 // torch.nan_to_num(v, 0, 0): nan -> 0, +inf -> 0, -inf -> the lowest finite float
 __device__ __forceinline__ float nan_to_num0(float v)
@@ -75,12 +55,7 @@ __device__ __forceinline__ float nan_to_num0(float v)
 // render/__init__.py:129-132 followed by Densify.py:14
 __device__ __forceinline__ float rendered_depth(const DepthCfg& c, float D, float A)
 {
-    float d = D;
-    if (c.use_weight_norm) {
-        d = D / (A + c.eps);
-        if (d > c.far || d < c.near) d = 0.f;
-    }
-    return nan_to_num0(d);
+    return nan_to_num0(normalised_depth(c, D, A));
 }
 
 // Walks `npass` finished digit histograms: prefix = the leading 8*npass bits of the element of rank `rank`, k = its rank among
@@ -243,35 +218,6 @@ __device__ __forceinline__ D3 world_point_d(const Cam& k, const float* __restric
             ((c[8] * px + c[9] * py) + c[10] * zd) + c[11]};
 }
 
-// pytorch3d's matrix_to_quaternion of R = [v0 v1 v2] (columns), as gs2d_pose_quat and gaus_slam_amd/tracking.py restate it:
-// four candidates from the diagonal, the best-conditioned one wins (first maximum on ties), real part >= 0.  A NaN entry
-// makes its q_abs zero (_sqrt_positive_part), as fmaxf does here.
-__device__ __forceinline__ void frame_to_quat(V3 v0, V3 v1, V3 v2, float q_out[4])
-{
-    const float m00 = v0.x, m01 = v1.x, m02 = v2.x, m10 = v0.y, m11 = v1.y, m12 = v2.y, m20 = v0.z, m21 = v1.z, m22 = v2.z;
-    const float qa[4] = {sqrtf(fmaxf(((1.0f + m00) + m11) + m22, 0.f)), sqrtf(fmaxf(((1.0f + m00) - m11) - m22, 0.f)),
-                         sqrtf(fmaxf(((1.0f - m00) + m11) - m22, 0.f)), sqrtf(fmaxf(((1.0f - m00) - m11) + m22, 0.f))};
-    const float cand[4][4] = {{qa[0] * qa[0], m21 - m12, m02 - m20, m10 - m01},
-                              {m21 - m12, qa[1] * qa[1], m10 + m01, m02 + m20},
-                              {m02 - m20, m10 + m01, qa[2] * qa[2], m12 + m21},
-                              {m10 - m01, m20 + m02, m21 + m12, qa[3] * qa[3]}};
-    int best = 0;
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        if (qa[i] > qa[best]) best = i;
-    float q[4];
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-        if (b == best) {
-            const float den = 2.0f * fmaxf(qa[b], 0.1f);
-#pragma unroll
-            for (int i = 0; i < 4; i++) q[i] = cand[b][i] / den;
-        }
-    const bool neg = q[0] < 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) q_out[i] = neg ? -q[i] : q[i];
-}
-
 struct SeedOut { float *means3D, *opacities, *scales, *rotations, *colors; int* pixel_index; };
 
 __device__ __forceinline__ void write_seed(int mode, int W, int H, int i, size_t row, const Cam& k, const float* __restrict__ c2w,
@@ -310,7 +256,7 @@ __device__ __forceinline__ void write_seed(int mode, int W, int H, int i, size_t
         v0 = divs(v0, norm(v0));
         V3 v1 = cross(v2, v0);
         v1 = divs(v1, norm(v1));
-        frame_to_quat(v0, v1, v2, q);
+        matrix_to_quaternion(v0.x, v1.x, v2.x, v0.y, v1.y, v2.y, v0.z, v1.z, v2.z, q);  // of R = [v0 v1 v2], columns
 #pragma unroll
         for (int j = 0; j < 4; j++) q[j] = nan_to_num0(q[j]);
         if (sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]) < 1e-3f) { q[0] = 1.f; q[1] = q[2] = q[3] = 0.f; }
@@ -362,43 +308,28 @@ prune_flag_kernel(int P, const float* __restrict__ opac, const float* __restrict
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
-struct CompactArrays {
-    int n;
-    const float* src[GS2D_MAP_MAX_ARRAYS];
-    float* dst[GS2D_MAP_MAX_ARRAYS];
-    int width[GS2D_MAP_MAX_ARRAYS];
-};
-
 // One workgroup per 1024 source rows: the kept rows of the block are listed in LDS in order, then every array is copied with
 // consecutive threads writing consecutive floats of its destination (the reads are as dense as the kept rows are).
 __global__ void __launch_bounds__(256)
-compact_kernel(CompactArrays A, int P, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ block_sums)
+compact_kernel(ArrayTable A, int P, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ block_sums)
 {
-    __shared__ uint32_t kept[ITEMS];
-    const int i0 = blockIdx.x * ITEMS + 4 * threadIdx.x;
+    __shared__ uint16_t kept[ITEMS];
+    const int row0 = blockIdx.x * ITEMS, t4 = 4 * threadIdx.x;
     bool f[4];
     uint32_t cnt = 0;
 #pragma unroll
-    for (int j = 0; j < 4; j++) { f[j] = i0 + j < P && flags[i0 + j] != 0; cnt += f[j] ? 1u : 0u; }
+    for (int j = 0; j < 4; j++) { f[j] = row0 + t4 + j < P && flags[row0 + t4 + j] != 0; cnt += f[j] ? 1u : 0u; }
     uint32_t total;
     uint32_t pos = block_incl_scan(cnt, &total) - cnt;
 #pragma unroll
     for (int j = 0; j < 4; j++)
-        if (f[j]) kept[pos++] = (uint32_t)(i0 + j);
+        if (f[j]) kept[pos++] = (uint16_t)(t4 + j);
     __syncthreads();
     if (total == 0) return;
     const size_t out0 = block_sums[blockIdx.x];
-#pragma unroll
-    for (int a = 0; a < GS2D_MAP_MAX_ARRAYS; a++) {
-        if (a >= A.n) break;
+    for (int a = 0; a < A.n; a++) {
         const uint32_t w = (uint32_t)A.width[a];
-        const float* __restrict__ src = A.src[a];
-        float* __restrict__ dst = A.dst[a] + out0 * w;
-        const uint32_t ne = total * w;
-        for (uint32_t e = threadIdx.x; e < ne; e += 256) {
-            const uint32_t j = e / w, c = e - j * w;
-            dst[e] = src[(size_t)kept[j] * w + c];
-        }
+        copy_rows(w, A.dst[a] + out0 * w, A.src[a] + (size_t)row0 * w, kept, total);
     }
 }
 
@@ -407,17 +338,13 @@ int read_count(const void* ws, hipStream_t s, const char* what)
     uint32_t n = 0;
     hipError_t e = hipMemcpyAsync(&n, (const uint32_t*)ws + GS2D_MAP_WS_COUNT, sizeof(n), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail_hip(what, e);
+    if (e != hipSuccess) return gs2d_map_fail_hip(what, e);
     return (int)n;
 }
 
 bool bad_size(int W, int H) { return W < 1 || H < 1 || (long long)W * H > (1ll << 30); }
 
 }  // namespace
-
-// the error text of this thread, for the other sources of the library (gs2d_map_densify.hip); not part of the C ABI
-__attribute__((visibility("hidden"))) int gs2d_map_fail(const char* msg) { return fail(msg); }
-__attribute__((visibility("hidden"))) int gs2d_map_fail_hip(const char* what, hipError_t e) { return fail_hip(what, e); }
 
 #ifndef GS2D_MAP_SOURCE_HASH
 #define GS2D_MAP_SOURCE_HASH "unknown"   /* gaus_slam_amd/build.py passes the hash of csrc_map/ + the C-ABI header */
@@ -428,7 +355,7 @@ extern "C" {
 const char* gs2d_map_build_info(void) { return "gs2d-map-hip gfx950 strict-fp (fp-contract=off) " __DATE__ " src " GS2D_MAP_SOURCE_HASH; }
 const char* gs2d_map_last_error(void) { return g_err; }
 
-size_t gs2d_map_seed_ws_bytes(int width, int height) { return bad_size(width, height) ? 0 : seed_layout(width, height).total; }
+size_t gs2d_map_seed_ws_bytes(int width, int height) { return bad_size(width, height) ? 0 : seed_layout(width, height).rows.total; }
 size_t gs2d_map_prune_ws_bytes(int P) { return P < 0 || P > (1 << 30) ? 0 : prune_layout(P).total; }
 
 int gs2d_map_seed_select(int mode, int width, int height, const float* allmap, const float* gt_depth, float sil_thres,
@@ -436,10 +363,10 @@ int gs2d_map_seed_select(int mode, int width, int height, const float* allmap, c
                          void* stream)
 {
     if (mode != GS2D_MAP_MODE_SPLATAM && mode != GS2D_MAP_MODE_EDGE && mode != GS2D_MAP_MODE_ALL)
-        return fail("gs2d_map_seed_select: mode must be 0 (splatam), 1 (edge growth) or 2 (all)");
-    if (bad_size(width, height)) return fail("gs2d_map_seed_select: width and height must be >= 1 and width*height <= 2^30");
-    if ((!allmap && mode != GS2D_MAP_MODE_ALL) || !gt_depth || !ws) return fail("gs2d_map_seed_select: NULL pointer");
-    if (((uintptr_t)ws | (uintptr_t)allmap | (uintptr_t)gt_depth) & 3) return fail("gs2d_map_seed_select: misaligned pointer");
+        return gs2d_map_fail("gs2d_map_seed_select: mode must be 0 (splatam), 1 (edge growth) or 2 (all)");
+    if (bad_size(width, height)) return gs2d_map_fail("gs2d_map_seed_select: width and height must be >= 1 and width*height <= 2^30");
+    if ((!allmap && mode != GS2D_MAP_MODE_ALL) || !gt_depth || !ws) return gs2d_map_fail("gs2d_map_seed_select: NULL pointer");
+    if (misaligned(ws) || misaligned(allmap) || misaligned(gt_depth)) return gs2d_map_fail("gs2d_map_seed_select: misaligned pointer");
     hipStream_t s = (hipStream_t)stream;
     const SeedLayout L = seed_layout(width, height);
     const int N = width * height;
@@ -447,22 +374,21 @@ int gs2d_map_seed_select(int mode, int width, int height, const float* allmap, c
     uint32_t* header = (uint32_t*)w;
     uint32_t* hist = (uint32_t*)(w + L.hist);
     uint32_t* zbuf = (uint32_t*)(w + L.zbuf);
-    uint8_t* flags = (uint8_t*)(w + L.flags);
-    uint32_t* block_sums = (uint32_t*)(w + L.block_sums);
+    uint8_t* flags = (uint8_t*)(w + L.rows.flags);
+    uint32_t* block_sums = (uint32_t*)(w + L.rows.sums);
     hipError_t e = hipMemsetAsync(ws, 0, HDR_BYTES + HIST_BYTES, s);
-    if (e != hipSuccess) return fail_hip("gs2d_map_seed_select: memset", e);
+    if (e != hipSuccess) return gs2d_map_fail_hip("gs2d_map_seed_select: memset", e);
     const DepthCfg dc{use_weight_norm != 0, eps, depth_near, depth_far};
     const uint32_t rank = (uint32_t)((N - 1) / 2);  // torch.median: the LOWER median
-    const dim3 grid((unsigned)L.nblk), block(256);
+    const dim3 grid((unsigned)L.rows.nblk), block(256);
     if (mode == GS2D_MAP_MODE_SPLATAM) {
         hipLaunchKernelGGL(seed_err_kernel, grid, block, 0, s, dc, N, allmap, gt_depth, zbuf, hist);
         for (int pass = 1; pass < 4; pass++) hipLaunchKernelGGL(seed_hist_kernel, grid, block, 0, s, pass, N, rank, zbuf, hist);
     }
     const SelectCfg c{mode, width, height, sil_thres, edge_thres, dc};
     hipLaunchKernelGGL(seed_flag_kernel, grid, block, 0, s, c, N, rank, allmap, gt_depth, zbuf, hist, flags, block_sums, header);
-    hipLaunchKernelGGL(map_scan_blocksums_kernel, dim3(1), dim3(SCAN_T), 0, s, block_sums, L.nblk, header + GS2D_MAP_WS_COUNT);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("gs2d_map_seed_select: launch", e);
+    hipLaunchKernelGGL(map_scan_blocksums_kernel, dim3(1), dim3(SCAN_T), 0, s, block_sums, L.rows.nblk, header + GS2D_MAP_WS_COUNT);
+    if (launched("gs2d_map_seed_select: launch")) return -1;
     return read_count(ws, s, "gs2d_map_seed_select: reading the seed count");
 }
 
@@ -471,67 +397,56 @@ int gs2d_map_seed_write(int mode, int width, int height, const float* allmap, co
                         float* opacities, float* scales, float* rotations, float* colors, int* pixel_index, void* stream)
 {
     if (mode != GS2D_MAP_MODE_SPLATAM && mode != GS2D_MAP_MODE_EDGE && mode != GS2D_MAP_MODE_ALL)
-        return fail("gs2d_map_seed_write: mode must be 0 (splatam), 1 (edge growth) or 2 (all)");
-    if (bad_size(width, height)) return fail("gs2d_map_seed_write: width and height must be >= 1 and width*height <= 2^30");
+        return gs2d_map_fail("gs2d_map_seed_write: mode must be 0 (splatam), 1 (edge growth) or 2 (all)");
+    if (bad_size(width, height)) return gs2d_map_fail("gs2d_map_seed_write: width and height must be >= 1 and width*height <= 2^30");
     if ((!allmap && mode != GS2D_MAP_MODE_ALL) || !gt_color_hwc || !gt_depth || !c2w || !ws || !means3D || !opacities || !scales || !rotations || !colors)
-        return fail("gs2d_map_seed_write: NULL pointer");
-    if (((uintptr_t)ws | (uintptr_t)gt_color_hwc | (uintptr_t)gt_depth | (uintptr_t)c2w | (uintptr_t)means3D | (uintptr_t)opacities |
-         (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)colors | (uintptr_t)pixel_index) & 3)
-        return fail("gs2d_map_seed_write: misaligned pointer");
+        return gs2d_map_fail("gs2d_map_seed_write: NULL pointer");
+    if (misaligned(ws) || misaligned(gt_color_hwc) || misaligned(gt_depth) || misaligned(c2w) || misaligned(means3D) || misaligned(opacities) ||
+        misaligned(scales) || misaligned(rotations) || misaligned(colors) || misaligned(pixel_index))
+        return gs2d_map_fail("gs2d_map_seed_write: misaligned pointer");
     const SeedLayout L = seed_layout(width, height);
     const char* w = (const char*)ws;
     const float* zsrc = mode == GS2D_MAP_MODE_EDGE ? (const float*)(w + L.zbuf) : gt_depth;
     const SeedOut o{means3D, opacities, scales, rotations, colors, pixel_index};
-    hipLaunchKernelGGL(seed_write_kernel, dim3((unsigned)L.nblk), dim3(256), 0, (hipStream_t)stream, mode, width, height,
-                       Cam{fx, fy, cx, cy}, c2w, activated != 0, zsrc, gt_color_hwc, (const uint8_t*)(w + L.flags),
-                       (const uint32_t*)(w + L.block_sums), o);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("gs2d_map_seed_write: launch", e);
+    hipLaunchKernelGGL(seed_write_kernel, dim3((unsigned)L.rows.nblk), dim3(256), 0, (hipStream_t)stream, mode, width, height,
+                       Cam{fx, fy, cx, cy}, c2w, activated != 0, zsrc, gt_color_hwc, (const uint8_t*)(w + L.rows.flags),
+                       (const uint32_t*)(w + L.rows.sums), o);
+    return launched("gs2d_map_seed_write: launch");
 }
 
 int gs2d_map_prune_select(int P, const float* opacities, const float* scales, int activated, float opacity_cull,
                           float scale_cull, float scale_max, void* ws, void* stream)
 {
-    if (P < 0 || P > (1 << 30)) return fail("gs2d_map_prune_select: P must be in [0, 2^30]");
-    if (!ws) return fail("gs2d_map_prune_select: NULL workspace");
+    if (P < 0 || P > (1 << 30)) return gs2d_map_fail("gs2d_map_prune_select: P must be in [0, 2^30]");
+    if (!ws) return gs2d_map_fail("gs2d_map_prune_select: NULL workspace");
     if (P == 0) return 0;
-    if (!opacities || !scales) return fail("gs2d_map_prune_select: NULL pointer");
-    if (((uintptr_t)ws | (uintptr_t)opacities | (uintptr_t)scales) & 3) return fail("gs2d_map_prune_select: misaligned pointer");
+    if (!opacities || !scales) return gs2d_map_fail("gs2d_map_prune_select: NULL pointer");
+    if (misaligned(ws) || misaligned(opacities) || misaligned(scales)) return gs2d_map_fail("gs2d_map_prune_select: misaligned pointer");
     hipStream_t s = (hipStream_t)stream;
-    const PruneLayout L = prune_layout(P);
+    const RowLayout L = prune_layout(P);
     char* w = (char*)ws;
-    uint32_t* block_sums = (uint32_t*)(w + L.block_sums);
+    uint32_t* block_sums = (uint32_t*)(w + L.sums);
     hipLaunchKernelGGL(prune_flag_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, P, opacities, scales, activated != 0, opacity_cull,
                        scale_cull, scale_max, (uint8_t*)(w + L.flags), block_sums);
     hipLaunchKernelGGL(map_scan_blocksums_kernel, dim3(1), dim3(SCAN_T), 0, s, block_sums, L.nblk, (uint32_t*)w + GS2D_MAP_WS_COUNT);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("gs2d_map_prune_select: launch", e);
+    if (launched("gs2d_map_prune_select: launch")) return -1;
     return read_count(ws, s, "gs2d_map_prune_select: reading the kept count");
 }
 
 int gs2d_map_compact(int P, const void* ws, int n_arrays, const float* const* src, float* const* dst, const int* widths,
                      void* stream)
 {
-    if (P < 0 || P > (1 << 30)) return fail("gs2d_map_compact: P must be in [0, 2^30]");
-    if (n_arrays < 0 || n_arrays > GS2D_MAP_MAX_ARRAYS) return fail("gs2d_map_compact: n_arrays must be in [0, GS2D_MAP_MAX_ARRAYS]");
+    if (P < 0 || P > (1 << 30)) return gs2d_map_fail("gs2d_map_compact: P must be in [0, 2^30]");
+    if (n_arrays < 0 || n_arrays > GS2D_MAP_MAX_ARRAYS) return gs2d_map_fail("gs2d_map_compact: n_arrays must be in [0, GS2D_MAP_MAX_ARRAYS]");
     if (P == 0 || n_arrays == 0) return 0;
-    if (!ws || !src || !dst || !widths) return fail("gs2d_map_compact: NULL pointer");
-    CompactArrays A;
-    A.n = n_arrays;
-    for (int a = 0; a < GS2D_MAP_MAX_ARRAYS; a++) {
-        const bool on = a < n_arrays;
-        if (on && (widths[a] < 1 || widths[a] > 4)) return fail("gs2d_map_compact: widths must be in [1, 4]");
-        if (on && (!src[a] || (((uintptr_t)src[a] | (uintptr_t)dst[a]) & 3))) return fail("gs2d_map_compact: NULL or misaligned array");
-        A.src[a] = on ? src[a] : nullptr;
-        A.dst[a] = on ? dst[a] : nullptr;  // may be NULL when nothing is kept: no row is stored then
-        A.width[a] = on ? widths[a] : 1;
-    }
-    const PruneLayout L = prune_layout(P);
+    if (!ws || !src || !dst || !widths) return gs2d_map_fail("gs2d_map_compact: NULL pointer");
+    ArrayTable A;
+    if (fill_arrays(A, "gs2d_map_compact", "NULL or misaligned array", n_arrays, src, dst, widths)) return -1;
+    const RowLayout L = prune_layout(P);
     const char* w = (const char*)ws;
     hipLaunchKernelGGL(compact_kernel, dim3((unsigned)L.nblk), dim3(256), 0, (hipStream_t)stream, A, P, (const uint8_t*)(w + L.flags),
-                       (const uint32_t*)(w + L.block_sums));
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("gs2d_map_compact: launch", e);
+                       (const uint32_t*)(w + L.sums));
+    return launched("gs2d_map_compact: launch");
 }
 
 }  // extern "C"

@@ -13,34 +13,16 @@
 // A clone is an unchanged copy of its source row, so it shares the row's prune decision; the two children of a row share
 // everything the prune reads (raw opacity, log(exp(s) / 1.6)), so they share theirs.
 #include "../csrc/gs2d_scan.h"
-#include "../../include/gs2d_map.h"
-#include <math.h>
-
-int gs2d_map_fail(const char* msg);                       // gs2d_map.hip: the thread's gs2d_map_last_error() text
-int gs2d_map_fail_hip(const char* what, hipError_t e);
+#include "gs2d_map_internal.h"
 
 namespace {
 
-constexpr int ITEMS = GS2D_SCAN_ITEMS;  // 1024 = 256 threads x 4
-constexpr size_t HDR_BYTES = 256;
 constexpr int NSUM = 5;                 // block counts: kept old, kept clones, kept split parents | cloned, split before the prune
 constexpr int MAX_P = 1 << 29;          // 3 P rows must fit an int
 constexpr uint8_t F_OLD = 1, F_CLONE = 2, F_CHILD = 4;
 constexpr int ROUND = 256;              // split parents evaluated per round of the write kernel
 
-struct DensifyLayout { size_t flags, sums, total; int nblk, stride; };
-DensifyLayout densify_layout(int P)
-{
-    DensifyLayout L;
-    const size_t n = (size_t)(P > 0 ? P : 1);
-    L.nblk = (int)((n + ITEMS - 1) / ITEMS);
-    L.stride = L.nblk + 64;
-    size_t o = HDR_BYTES;
-    L.flags = o; o = gs2d_align_up(o + n, 256);
-    L.sums = o; o = gs2d_align_up(o + 4 * (size_t)NSUM * L.stride, 256);
-    L.total = o;
-    return L;
-}
+RowLayout densify_layout(int P) { return row_layout((size_t)(P > 0 ? P : 1), NSUM); }
 
 // ----------------------------------------------------------------------------------------------------------------- statistics
 __global__ void __launch_bounds__(256)
@@ -134,21 +116,10 @@ __global__ void __launch_bounds__(SCAN_T) densify_scan_kernel(uint32_t* sums, in
 struct DensifyArrays {
     const float* psrc[5];   // means3D [P,3], opacities [P,1], scales [P,2], rotations [P,4], colors [P,3]
     float* pdst[5];
-    int n_mom;
-    const float* msrc[GS2D_MAP_MAX_ARRAYS];
-    float* mdst[GS2D_MAP_MAX_ARRAYS];
-    int mwidth[GS2D_MAP_MAX_ARRAYS];
+    ArrayTable mom;         // both Adam moments of each
 };
 
-// dst[0 .. n W) = the rows list[0 .. n) of src (row indices local to the block, src points at the block's first row)
-template <int W>
-__device__ __forceinline__ void copy_rows(float* __restrict__ dst, const float* __restrict__ src, const uint16_t* list, uint32_t n)
-{
-    for (uint32_t e = threadIdx.x; e < n * W; e += 256) {
-        const uint32_t j = e / W, c = e - j * W;
-        dst[e] = src[(uint32_t)list[j] * W + c];
-    }
-}
+// copy_rows (gs2d_map_internal.h) into two destinations
 template <int W>
 __device__ __forceinline__ void copy_rows_twice(float* __restrict__ dst0, float* __restrict__ dst1, const float* __restrict__ src,
                                                 const uint16_t* list, uint32_t n)
@@ -219,24 +190,17 @@ densify_write_kernel(DensifyArrays A, int P, const uint32_t* __restrict__ flag_w
     copy_rows_twice<3>(A.pdst[4] + 3 * o_ch0, A.pdst[4] + 3 * o_ch1, A.psrc[4] + 3 * r0, l_child, n_child);
 
     // moments: old rows keep theirs, every new row starts from zero
-    for (int a = 0; a < A.n_mom; a++) {
-        const uint32_t w = (uint32_t)A.mwidth[a];
-        const float* __restrict__ src = A.msrc[a] + r0 * w;
-        float* __restrict__ dst = A.mdst[a];
-        float* __restrict__ d_old = dst + o_old * w;
-        switch (w) {  // a constant divisor in the copy loop
-        case 1: copy_rows<1>(d_old, src, l_old, n_old); break;
-        case 2: copy_rows<2>(d_old, src, l_old, n_old); break;
-        case 3: copy_rows<3>(d_old, src, l_old, n_old); break;
-        default: copy_rows<4>(d_old, src, l_old, n_old); break;
-        }
+    for (int a = 0; a < A.mom.n; a++) {
+        const uint32_t w = (uint32_t)A.mom.width[a];
+        float* __restrict__ dst = A.mom.dst[a];
+        copy_rows(w, dst + o_old * w, A.mom.src[a] + r0 * w, l_old, n_old);
         fill_zero(dst + o_clone * w, n_clone * w);
         fill_zero(dst + o_ch0 * w, n_child * w);
         fill_zero(dst + o_ch1 * w, n_child * w);
     }
 
     // children: means3D = xyz + R(q) (exp(s0) n0, exp(s1) n1, 0) per copy, scales = log(exp(s) / 1.6) for both copies.
-    // R is pytorch3d's quaternion_to_matrix of the RAW quaternion (two_s = 2 / |q|^2); only its first two columns are needed.
+    // R is pytorch3d's quaternion_to_matrix of the RAW quaternion; only its first two columns are needed.
     for (uint32_t base = 0; base < n_child; base += ROUND) {  // n_child is uniform over the block
         const uint32_t n = min((uint32_t)ROUND, n_child - base), j = base + threadIdx.x;
         if (j < n_child) {
@@ -245,18 +209,15 @@ densify_write_kernel(DensifyArrays A, int P, const uint32_t* __restrict__ flag_w
             const float* __restrict__ x = A.psrc[0] + 3 * row;
             const float* __restrict__ nz = noise + 4 * row;
             const float e0 = expf(A.psrc[2][2 * row]), e1 = expf(A.psrc[2][2 * row + 1]);
-            const float r = q[0], i = q[1], jj = q[2], k = q[3];
-            const float two_s = 2.0f / (((r * r + i * i) + jj * jj) + k * k);
-            const float R00 = 1.f - two_s * (jj * jj + k * k), R01 = two_s * (i * jj - k * r);
-            const float R10 = two_s * (i * jj + k * r), R11 = 1.f - two_s * (i * i + k * k);
-            const float R20 = two_s * (i * k - jj * r), R21 = two_s * (jj * k + i * r);
+            float R[9];
+            quaternion_to_matrix(q[0], q[1], q[2], q[3], R);
             const float x0 = x[0], x1 = x[1], x2 = x[2];
 #pragma unroll
             for (int cp = 0; cp < 2; cp++) {
                 const float a = e0 * nz[2 * cp], b = e1 * nz[2 * cp + 1];
-                st_xyz[cp][3 * threadIdx.x] = (R00 * a + R01 * b) + x0;
-                st_xyz[cp][3 * threadIdx.x + 1] = (R10 * a + R11 * b) + x1;
-                st_xyz[cp][3 * threadIdx.x + 2] = (R20 * a + R21 * b) + x2;
+                st_xyz[cp][3 * threadIdx.x] = (R[0] * a + R[1] * b) + x0;
+                st_xyz[cp][3 * threadIdx.x + 1] = (R[3] * a + R[4] * b) + x1;
+                st_xyz[cp][3 * threadIdx.x + 2] = (R[6] * a + R[7] * b) + x2;
             }
             st_sc[2 * threadIdx.x] = logf(e0 / 1.6f);
             st_sc[2 * threadIdx.x + 1] = logf(e1 / 1.6f);
@@ -271,8 +232,6 @@ densify_write_kernel(DensifyArrays A, int P, const uint32_t* __restrict__ flag_w
         __syncthreads();
     }
 }
-
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
 
 }  // namespace
 
@@ -289,8 +248,7 @@ int gs2d_map_densify_stats(int P, const int* radii, const float* dL_dmean2D, flo
         return gs2d_map_fail("gs2d_map_densify_stats: misaligned pointer");
     hipLaunchKernelGGL(densify_stats_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, radii,
                        dL_dmean2D, accum, denom);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_map_densify_stats: launch", e);
+    return launched("gs2d_map_densify_stats: launch");
 }
 
 int gs2d_map_densify_select(int P, const float* opacities, const float* scales, const float* accum, const float* denom,
@@ -307,17 +265,16 @@ int gs2d_map_densify_select(int P, const float* opacities, const float* scales, 
     if (misaligned(ws) || misaligned(opacities) || misaligned(scales) || misaligned(accum) || misaligned(denom))
         return gs2d_map_fail("gs2d_map_densify_select: misaligned pointer");
     hipStream_t s = (hipStream_t)stream;
-    const DensifyLayout L = densify_layout(P);
+    const RowLayout L = densify_layout(P);
     char* w = (char*)ws;
     uint32_t* sums = (uint32_t*)(w + L.sums);
     const DensifyCfg c{grad_threshold, dense_size, opacity_cull, scale_cull, world_max};
     hipLaunchKernelGGL(densify_flag_kernel, dim3((unsigned)L.nblk), dim3(256), 0, s, c, P, opacities, scales, accum, denom,
                        (uint32_t*)(w + L.flags), sums, L.stride);
     hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(SCAN_T), 0, s, sums, L.stride, L.nblk, (uint32_t*)w);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gs2d_map_fail_hip("gs2d_map_densify_select: launch", e);
+    if (launched("gs2d_map_densify_select: launch")) return -1;
     uint32_t h[GS2D_MAP_WS_DENSIFY_WORDS];
-    e = hipMemcpyAsync(h, ws, sizeof(h), hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(h, ws, sizeof(h), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return gs2d_map_fail_hip("gs2d_map_densify_select: reading the row counts", e);
     if (counts)
@@ -343,22 +300,13 @@ int gs2d_map_densify_write(int P, const void* ws, const float* noise, const floa
         A.psrc[a] = param_src[a];
         A.pdst[a] = param_dst[a];
     }
-    A.n_mom = n_moments;
-    for (int a = 0; a < GS2D_MAP_MAX_ARRAYS; a++) {
-        const bool on = a < n_moments;
-        if (on && (moment_widths[a] < 1 || moment_widths[a] > 4)) return gs2d_map_fail("gs2d_map_densify_write: widths must be in [1, 4]");
-        if (on && (!moment_src[a] || misaligned(moment_src[a]) || misaligned(moment_dst[a])))
-            return gs2d_map_fail("gs2d_map_densify_write: NULL or misaligned moment array");
-        A.msrc[a] = on ? moment_src[a] : nullptr;
-        A.mdst[a] = on ? moment_dst[a] : nullptr;
-        A.mwidth[a] = on ? moment_widths[a] : 1;
-    }
-    const DensifyLayout L = densify_layout(P);
+    if (fill_arrays(A.mom, "gs2d_map_densify_write", "NULL or misaligned moment array", n_moments, moment_src, moment_dst, moment_widths))
+        return -1;
+    const RowLayout L = densify_layout(P);
     const char* w = (const char*)ws;
     hipLaunchKernelGGL(densify_write_kernel, dim3((unsigned)L.nblk), dim3(256), 0, (hipStream_t)stream, A, P,
                        (const uint32_t*)(w + L.flags), (const uint32_t*)(w + L.sums), L.stride, (const uint32_t*)w, noise);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_map_densify_write: launch", e);
+    return launched("gs2d_map_densify_write: launch");
 }
 
 }  // extern "C"

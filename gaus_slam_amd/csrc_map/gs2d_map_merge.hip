@@ -24,13 +24,7 @@
 // The rotation of a new row is evaluated in float64 on the float32 inputs (R(q), the product with the transfer's rotation,
 // matrix_to_quaternion, a final normalisation) and rounded once: a few hundred operations for each of n rows, beside a
 // stream of 39 (P + n) floats.
-#include <hip/hip_runtime.h>
-#include "../../include/gs2d_map.h"
-#include <math.h>
-#include <stdint.h>
-
-int gs2d_map_fail(const char* msg);                       // gs2d_map.hip: the thread's gs2d_map_last_error() text
-int gs2d_map_fail_hip(const char* what, hipError_t e);
+#include "gs2d_map_internal.h"
 
 namespace {
 
@@ -100,33 +94,6 @@ __device__ __forceinline__ void means_chunk(const Seg& g, uint32_t k, const floa
     o[2] = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
 }
 
-// pytorch3d's matrix_to_quaternion (as frame_to_quat in gs2d_map.hip restates it), in float64, of m = [row-major 3x3]
-__device__ __forceinline__ void matrix_to_quat(const double m[9], double q_out[4])
-{
-    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    const double qa[4] = {sqrt(fmax(((1.0 + m00) + m11) + m22, 0.0)), sqrt(fmax(((1.0 + m00) - m11) - m22, 0.0)),
-                          sqrt(fmax(((1.0 - m00) + m11) - m22, 0.0)), sqrt(fmax(((1.0 - m00) - m11) + m22, 0.0))};
-    const double cand[4][4] = {{qa[0] * qa[0], m21 - m12, m02 - m20, m10 - m01},
-                               {m21 - m12, qa[1] * qa[1], m10 + m01, m02 + m20},
-                               {m02 - m20, m10 + m01, qa[2] * qa[2], m12 + m21},
-                               {m10 - m01, m20 + m02, m21 + m12, qa[3] * qa[3]}};
-    int best = 0;
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        if (qa[i] > qa[best]) best = i;
-    double q[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-        if (b == best) {
-            const double den = 2.0 * fmax(qa[b], 0.1);
-#pragma unroll
-            for (int i = 0; i < 4; i++) q[i] = cand[b][i] / den;
-        }
-    const bool neg = q[0] < 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) q_out[i] = neg ? -q[i] : q[i];
-}
-
 // rotations = normalised matrix_to_quaternion(R_t R(q)), R(q) pytorch3d's quaternion_to_matrix of the RAW quaternion
 __device__ __forceinline__ void rot_chunk(const Seg& g, uint32_t k, const float* __restrict__ T)
 {
@@ -136,11 +103,8 @@ __device__ __forceinline__ void rot_chunk(const Seg& g, uint32_t k, const float*
     float4 qf;
     if (g.src_vec) qf = *reinterpret_cast<const float4*>(p);
     else { qf.x = p[0]; qf.y = p[1]; qf.z = p[2]; qf.w = p[3]; }
-    const double r = qf.x, i = qf.y, j = qf.z, kk = qf.w;
-    const double two_s = 2.0 / (((r * r + i * i) + j * j) + kk * kk);
-    const double R[9] = {1.0 - two_s * (j * j + kk * kk), two_s * (i * j - kk * r), two_s * (i * kk + j * r),
-                         two_s * (i * j + kk * r), 1.0 - two_s * (i * i + kk * kk), two_s * (j * kk - i * r),
-                         two_s * (i * kk - j * r), two_s * (j * kk + i * r), 1.0 - two_s * (i * i + j * j)};
+    double R[9];
+    quaternion_to_matrix<double>(qf.x, qf.y, qf.z, qf.w, R);
     double M[9];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
@@ -149,7 +113,7 @@ __device__ __forceinline__ void rot_chunk(const Seg& g, uint32_t k, const float*
         for (int b = 0; b < 3; b++) M[3 * a + b] = (t0 * R[b] + t1 * R[3 + b]) + t2 * R[6 + b];
     }
     double q[4];
-    matrix_to_quat(M, q);
+    matrix_to_quaternion(M[0], M[1], M[2], M[3], M[4], M[5], M[6], M[7], M[8], q);
     const double len = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
     const float4 out = make_float4((float)(q[0] / len), (float)(q[1] / len), (float)(q[2] / len), (float)(q[3] / len));
     float* __restrict__ o = g.dst + 4 * row;
@@ -173,8 +137,6 @@ __global__ void __launch_bounds__(256) merge_kernel(MergeArgs A)
         }
     }
 }
-
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
 
 // appends a segment of `len` > 0 floats / rows; returns false when the pointers are unusable
 bool add_seg(MergeArgs& A, uint8_t kind, const float* src, float* dst, uint64_t len)
@@ -215,7 +177,7 @@ extern "C" int gs2d_map_merge(int P, int n, const float* const* param_src, const
         return gs2d_map_fail("gs2d_map_merge: n_moments must be in [0, GS2D_MAP_MAX_ARRAYS]");
     if (n_moments && !moment_widths) return gs2d_map_fail("gs2d_map_merge: NULL moment_widths");
     for (int a = 0; a < n_moments; a++)
-        if (moment_widths[a] < 1 || moment_widths[a] > 4) return gs2d_map_fail("gs2d_map_merge: widths must be in [1, 4]");
+        if (bad_width(moment_widths[a])) return fail_widths("gs2d_map_merge");
     if (opacity_cap != opacity_cap) return gs2d_map_fail("gs2d_map_merge: opacity_cap is NaN");
     if (P + n == 0) return 0;
     if (!param_dst || (P && !param_src) || (n && (!incoming || !transfer)) || (n_moments && (!moment_dst || (P && !moment_src))))
@@ -246,6 +208,5 @@ extern "C" int gs2d_map_merge(int P, int n, const float* const* param_src, const
 
     const unsigned grid = A.nchunk < (uint32_t)MAX_GRID ? A.nchunk : (unsigned)MAX_GRID;
     hipLaunchKernelGGL(merge_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, A);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_map_merge: launch", e);
+    return launched("gs2d_map_merge: launch");
 }

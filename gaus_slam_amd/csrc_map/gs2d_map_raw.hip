@@ -14,12 +14,7 @@
 //
 // The Adam update is adam_one of csrc/gs2d_adam.hip, statement for statement; both libraries are built with -ffp-contract=off
 // and IEEE division / square root, so gs2d_map_raw_step equals gs2d_adam_step on the raw gradient bit for bit.
-#include <hip/hip_runtime.h>
-#include "../../include/gs2d_map.h"
-#include <math.h>
-
-int gs2d_map_fail(const char* msg);                       // gs2d_map.hip: the thread's gs2d_map_last_error() text
-int gs2d_map_fail_hip(const char* what, hipError_t e);
+#include "gs2d_map_internal.h"
 
 namespace {
 
@@ -55,7 +50,8 @@ activate_kernel(size_t P, const float* __restrict__ o_raw, const float* __restri
 
 struct RawStepCfg { float step_size[5]; float one_m_b1, b2, one_m_b2, inv_bc2_sqrt, eps; };
 
-// adam_one of csrc/gs2d_adam.hip (torch/optim/adam.py _single_tensor_adam): keep the two in step
+// adam_one of csrc/gs2d_adam.hip (torch/optim/adam.py _single_tensor_adam): keep the two in step.  A copy on purpose: a shared
+// header would move the source hash of the rasterizer library.
 __device__ __forceinline__ void adam_one(float g, float& p, float& m, float& v, float one_m_b1, float b2, float one_m_b2,
                                          float inv_bc2_sqrt, float eps, float step_size)
 {
@@ -98,8 +94,6 @@ raw_step_kernel(RawStepCfg c, size_t P, float* __restrict__ param, const float* 
     }
 }
 
-bool misaligned(const void* p, uintptr_t a = 4) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 unsigned grid_for(size_t items)
 {
     const size_t blocks = (items + 255) / 256;
@@ -123,8 +117,7 @@ int gs2d_map_activate(int P, const float* opacities_raw, const float* scales_raw
     const size_t n = (size_t)P, total = round_up4(3 * n) + 4 * n;
     hipLaunchKernelGGL(activate_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, n, opacities_raw, scales_raw,
                        rotations_raw, opacities, scales, rotations);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_map_activate: launch", e);
+    return launched("gs2d_map_activate: launch");
 }
 
 int gs2d_map_raw_step(int P, float* param_flat, const float* act, const float* grad_flat, float* exp_avg, float* exp_avg_sq,
@@ -148,8 +141,7 @@ int gs2d_map_raw_step(int P, float* param_flat, const float* act, const float* g
     const size_t n = (size_t)P, total = round_up4(9 * n) + 4 * n;
     hipLaunchKernelGGL(raw_step_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, c, n, param_flat, act, grad_flat,
                        exp_avg, exp_avg_sq, raw_grad_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_map_raw_step: launch", e);
+    return launched("gs2d_map_raw_step: launch");
 }
 
 }  // extern "C"

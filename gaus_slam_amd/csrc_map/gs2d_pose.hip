@@ -10,12 +10,8 @@
 //                      any store: the latch.
 //   frame_stats:       a grid-stride pass with wave shuffles and per-workgroup partials in `ws`, then a one-workgroup fold:
 //                      two launches and no inter-workgroup hand-off inside a launch.
-#include <hip/hip_runtime.h>
+#include "gs2d_map_internal.h"
 #include "../../include/gs2d_pose.h"
-#include <math.h>
-
-int gs2d_map_fail(const char* msg);                       // gs2d_map.hip: the thread's gs2d_map_last_error() text
-int gs2d_map_fail_hip(const char* what, hipError_t e);
 
 namespace {
 
@@ -24,11 +20,10 @@ namespace {
 __device__ __forceinline__ void pose_matrix(const float q[4], const float t[3], float M[12])
 {
     const float n = fmaxf(sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]), 1e-12f);
-    const float r = q[0] / n, i = q[1] / n, j = q[2] / n, k = q[3] / n;
-    const float two_s = 2.0f / (((r * r + i * i) + j * j) + k * k);
-    M[0] = 1.f - two_s * (j * j + k * k); M[1] = two_s * (i * j - k * r);       M[2] = two_s * (i * k + j * r);        M[3] = t[0];
-    M[4] = two_s * (i * j + k * r);       M[5] = 1.f - two_s * (i * i + k * k); M[6] = two_s * (j * k - i * r);        M[7] = t[1];
-    M[8] = two_s * (i * k - j * r);       M[9] = two_s * (j * k + i * r);       M[10] = 1.f - two_s * (i * i + j * j); M[11] = t[2];
+    float R[9];
+    quaternion_to_matrix(q[0] / n, q[1] / n, q[2] / n, q[3] / n, R);
+#pragma unroll
+    for (int a = 0; a < 3; a++) { M[4 * a] = R[3 * a]; M[4 * a + 1] = R[3 * a + 1]; M[4 * a + 2] = R[3 * a + 2]; M[4 * a + 3] = t[a]; }
 }
 
 // Entry (row, col) of left [R t; 0 0 0 1], sums in index order; left == nullptr is the identity.  left's fourth row is taken
@@ -42,34 +37,6 @@ __device__ __forceinline__ float composed_entry(const float* __restrict__ left, 
     return v;
 }
 
-// pytorch3d.transforms.matrix_to_quaternion (as gaus_slam_amd/tracking.py:matrix_to_quaternion restates it): four candidates
-// from the diagonal, the best-conditioned one wins (first maximum on ties), real part >= 0.
-__device__ __forceinline__ void matrix_to_quat(const float* __restrict__ m, float q_out[4])
-{
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[4], m11 = m[5], m12 = m[6], m20 = m[8], m21 = m[9], m22 = m[10];
-    const float qa[4] = {sqrtf(fmaxf(((1.0f + m00) + m11) + m22, 0.f)), sqrtf(fmaxf(((1.0f + m00) - m11) - m22, 0.f)),
-                         sqrtf(fmaxf(((1.0f - m00) + m11) - m22, 0.f)), sqrtf(fmaxf(((1.0f - m00) - m11) + m22, 0.f))};
-    const float cand[4][4] = {{qa[0] * qa[0], m21 - m12, m02 - m20, m10 - m01},
-                              {m21 - m12, qa[1] * qa[1], m10 + m01, m02 + m20},
-                              {m02 - m20, m10 + m01, qa[2] * qa[2], m12 + m21},
-                              {m10 - m01, m20 + m02, m21 + m12, qa[3] * qa[3]}};
-    int best = 0;
-#pragma unroll
-    for (int i = 1; i < 4; i++)
-        if (qa[i] > qa[best]) best = i;
-    float q[4] = {1.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-        if (b == best) {
-            const float den = 2.0f * fmaxf(qa[b], 0.1f);
-#pragma unroll
-            for (int i = 0; i < 4; i++) q[i] = cand[b][i] / den;
-        }
-    const bool neg = q[0] < 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) q_out[i] = neg ? -q[i] : q[i];
-}
-
 __global__ void __launch_bounds__(64)
 pose_init_kernel(uint32_t* __restrict__ state, const float* __restrict__ w2c_init, const float* __restrict__ left,
                  float* __restrict__ w2c_out)
@@ -77,7 +44,8 @@ pose_init_kernel(uint32_t* __restrict__ state, const float* __restrict__ w2c_ini
     const int lane = threadIdx.x;
     float q[4] = {1.f, 0.f, 0.f, 0.f}, t[3] = {0.f, 0.f, 0.f};
     if (w2c_init) {
-        matrix_to_quat(w2c_init, q);
+        const float* __restrict__ m = w2c_init;  // row-major [3,4]
+        matrix_to_quaternion(m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10], q);
         t[0] = w2c_init[3]; t[1] = w2c_init[7]; t[2] = w2c_init[11];
     }
     float M[12];
@@ -203,7 +171,7 @@ pose_step_kernel(uint32_t* __restrict__ state, const float* __restrict__ G, cons
 // ------------------------------------------------------------------------------------------------------------ frame statistics
 constexpr int STATS_MAX_BLOCKS = GS2D_POSE_STATS_WS_DOUBLES / 3;  // 512: two workgroups per CU, as the loss reduction
 
-struct StatsCfg { int use_weight_norm; float eps, near, far, alpha_track, gt_min, alpha_key; };
+struct StatsCfg { DepthCfg dc; float alpha_track, gt_min, alpha_key; };
 
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -231,11 +199,7 @@ frame_stats_kernel(StatsCfg c, int HWi, const float* __restrict__ allmap, const 
     uint32_t n_mask = 0, n_key = 0;  // a thread sees at most 2^30 / 256 pixels
     for (size_t pix = (size_t)blockIdx.x * 256 + threadIdx.x; pix < HW; pix += (size_t)gridDim.x * 256) {
         const float D = allmap[pix], A = allmap[HW + pix], gt = gt_depth[pix];
-        float d = D;
-        if (c.use_weight_norm) {
-            d = D / (A + c.eps);
-            if (d > c.far || d < c.near) d = 0.f;
-        }
+        const float d = normalised_depth(c.dc, D, A);
         if (A > c.alpha_track && gt > c.gt_min) { sum += (double)fabsf(d - gt); n_mask++; }
         if (A < c.alpha_key) n_key++;
     }
@@ -257,8 +221,6 @@ __global__ void __launch_bounds__(256) frame_stats_fold_kernel(const double* __r
     }
 }
 
-bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -266,18 +228,17 @@ extern "C" {
 int gs2d_pose_init(void* state, const float* w2c_init, const float* left, float* w2c_out, void* stream)
 {
     if (!state || !w2c_out) return gs2d_map_fail("gs2d_pose_init: NULL pointer");
-    if (misaligned(state, 4) || misaligned(w2c_init, 4) || misaligned(left, 4) || misaligned(w2c_out, 4))
+    if (misaligned(state) || misaligned(w2c_init) || misaligned(left) || misaligned(w2c_out))
         return gs2d_map_fail("gs2d_pose_init: misaligned pointer");
     hipLaunchKernelGGL(pose_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)state, w2c_init, left, w2c_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_pose_init: launch", e);
+    return launched("gs2d_pose_init: launch");
 }
 
 int gs2d_pose_step(void* state, const float* dL_dw2c, const float* left, const float* next_left, gs2d_pose_cfg cfg,
                    float* w2c_out, void* stream)
 {
     if (!state || !dL_dw2c || !w2c_out) return gs2d_map_fail("gs2d_pose_step: NULL pointer");
-    if (misaligned(state, 4) || misaligned(dL_dw2c, 4) || misaligned(left, 4) || misaligned(next_left, 4) || misaligned(w2c_out, 4))
+    if (misaligned(state) || misaligned(dL_dw2c) || misaligned(left) || misaligned(next_left) || misaligned(w2c_out))
         return gs2d_map_fail("gs2d_pose_step: misaligned pointer");
     if (!(cfg.beta1 >= 0.0 && cfg.beta1 < 1.0 && cfg.beta2 >= 0.0 && cfg.beta2 < 1.0))
         return gs2d_map_fail("gs2d_pose_step: betas must be in [0, 1)");
@@ -285,8 +246,7 @@ int gs2d_pose_step(void* state, const float* dL_dw2c, const float* left, const f
     if (!(cfg.max_steps[0] > 0.0 && cfg.max_steps[1] > 0.0)) return gs2d_map_fail("gs2d_pose_step: max_steps must be > 0");
     hipLaunchKernelGGL(pose_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)state, dL_dw2c, left, next_left, cfg,
                        w2c_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_pose_step: launch", e);
+    return launched("gs2d_pose_step: launch");
 }
 
 int gs2d_pose_frame_stats(int width, int height, const float* allmap, const float* gt_depth, int use_weight_norm, float eps,
@@ -296,16 +256,15 @@ int gs2d_pose_frame_stats(int width, int height, const float* allmap, const floa
     if (width <= 0 || height <= 0 || (long long)width * height > (1ll << 30))
         return gs2d_map_fail("gs2d_pose_frame_stats: the image must have 1 <= W*H <= 2^30 pixels");
     if (!allmap || !gt_depth || !ws || !out) return gs2d_map_fail("gs2d_pose_frame_stats: NULL pointer");
-    if (misaligned(allmap, 4) || misaligned(gt_depth, 4) || misaligned(ws, 8) || misaligned(out, 8))
+    if (misaligned(allmap) || misaligned(gt_depth) || misaligned(ws, 8) || misaligned(out, 8))
         return gs2d_map_fail("gs2d_pose_frame_stats: misaligned pointer");
     const int HW = width * height;
     const int blocks = (HW + 255) / 256, grid = blocks < STATS_MAX_BLOCKS ? blocks : STATS_MAX_BLOCKS;
-    const StatsCfg c{use_weight_norm != 0, eps, depth_near, depth_far, alpha_track, gt_min, alpha_key};
+    const StatsCfg c{{use_weight_norm != 0, eps, depth_near, depth_far}, alpha_track, gt_min, alpha_key};
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(frame_stats_kernel, dim3((unsigned)grid), dim3(256), 0, s, c, HW, allmap, gt_depth, ws);
     hipLaunchKernelGGL(frame_stats_fold_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, grid, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gs2d_map_fail_hip("gs2d_pose_frame_stats: launch", e);
+    return launched("gs2d_pose_frame_stats: launch");
 }
 
 }  // extern "C"

@@ -30,7 +30,6 @@ import torch
 from . import _map_lib
 from .ba_shard import BUCKET_FIELDS, BUCKET_FLOATS
 from .optim import _views
-from .rasterizer import _on_device, _stream_ptr
 
 MODES = {"splatam": 0, "edge": 1, "all": 2}  # GS2D_MAP_MODE_*
 
@@ -110,14 +109,9 @@ def seed_select(allmap, gt_depth, *, mode="splatam", sil_thres=None, edge_thres=
     _require(sil_thres is not None, f"mode {mode!r} needs sil_thres")
     W, H = _check_frame(allmap, None, gt_depth, no_allmap=mode == "all")
     dev = gt_depth.device
-    L = _map_lib.lib()
-    ws = torch.empty(L.gs2d_map_seed_ws_bytes(W, H), dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        n = L.gs2d_map_seed_select(MODES[mode], W, H, _ptr(allmap), gt_depth.data_ptr(), float(sil_thres), float(edge_thres),
-                                   int(bool(use_weight_norm)), float(eps), float(depth_near), float(depth_far), ws.data_ptr(),
-                                   _stream_ptr(dev))
-    if n < 0:
-        raise RuntimeError(_map_lib.last_error())
+    ws = torch.empty(_map_lib.lib().gs2d_map_seed_ws_bytes(W, H), dtype=torch.uint8, device=dev)
+    n = _map_lib.call("gs2d_map_seed_select", dev, MODES[mode], W, H, _ptr(allmap), gt_depth.data_ptr(), float(sil_thres),
+                      float(edge_thres), int(bool(use_weight_norm)), float(eps), float(depth_near), float(depth_far), ws.data_ptr())
     return SeedSelection(n, ws, mode, W, H)
 
 
@@ -146,14 +140,9 @@ def seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pixel_inde
     fx, fy, cx, cy = _intrinsics(intrinsics)
     if sel.n == 0:
         return
-    with _on_device(dev):
-        rc = _map_lib.lib().gs2d_map_seed_write(
-            MODES[sel.mode], W, H, _ptr(allmap), gt_color.data_ptr(), gt_depth.data_ptr(), fx, fy, cx, cy, c2w.data_ptr(),
-            int(bool(activated)), sel.ws.data_ptr(), out["means3D"].data_ptr(), out["opacities"].data_ptr(),
-            out["scales"].data_ptr(), out["rotations"].data_ptr(), out["colors"].data_ptr(),
-            None if pixel_index is None else pixel_index.data_ptr(), _stream_ptr(dev))
-    if rc < 0:
-        raise RuntimeError(_map_lib.last_error())
+    _map_lib.call("gs2d_map_seed_write", dev, MODES[sel.mode], W, H, _ptr(allmap), gt_color.data_ptr(), gt_depth.data_ptr(), fx, fy,
+                  cx, cy, c2w.data_ptr(), int(bool(activated)), sel.ws.data_ptr(), *(out[name].data_ptr() for name in BUCKET_FIELDS),
+                  _ptr(pixel_index))
 
 
 def seed_from_frame(allmap, gt_color, gt_depth, intrinsics, w2c, *, mode="splatam", sil_thres=None, edge_thres=0.4,
@@ -216,6 +205,37 @@ def _grow(opt, n_new):
     return soa.views
 
 
+class _Realloc:
+    """The re-allocation every topology change ends in: three new flat buffers for `rows` rows (parameters, exp_avg,
+    exp_avg_sq; nothing is written here) and the ctypes pointer tables a write kernel takes -- `psrc` / `pdst` over the five
+    parameters (of type `vp5`), `msrc` / `mdst` / `widths` over the ten moments (`n_mom`), old buffers against new ones.  An
+    empty tensor has no address and is passed as NULL."""
+
+    def __init__(self, opt, rows):
+        soa = opt.soa
+        self.opt, self.rows = opt, rows
+        self.old = (soa.flat, opt.exp_avg, opt.exp_avg_sq)
+        self.new = [torch.empty(BUCKET_FLOATS * rows, dtype=torch.float32, device=soa.flat.device) for _ in range(3)]
+        ptrs = lambda buf, n: [v.data_ptr() or None for v in _views(buf, n).values()]
+        self.vp5 = C.c_void_p * len(BUCKET_FIELDS)  # the type of a table over the five parameters
+        table = lambda p: (C.c_void_p * len(p))(*p)
+        src, dst = [ptrs(b, soa.P) for b in self.old], [ptrs(b, rows) for b in self.new]
+        self.psrc, self.pdst = table(src[0]), table(dst[0])
+        self.msrc, self.mdst = table(src[1] + src[2]), table(dst[1] + dst[2])
+        self.n_mom = 2 * len(BUCKET_FIELDS)
+        self.widths = (C.c_int * self.n_mom)(*(2 * list(BUCKET_FIELDS.values())))
+
+    def adopt(self, *inputs):
+        """After the launch: the SoA and its optimizer take the new buffers.  The kernel still reads the old ones (and the
+        caller's further `inputs`) on the current stream; when they were allocated on another one, the caching allocator must
+        not hand them out there before it has finished."""
+        stream = torch.cuda.current_stream(self.new[0].device)
+        for t in (*self.old, *inputs):
+            if t.numel():
+                t.record_stream(stream)
+        _adopt(self.opt, *self.new, self.rows)
+
+
 def prune_gaussians(opt, opacity_cull, scale_cull, scale_max, activated=False):
     """Densify.prune_gaussians (Densify.py:43-50) on a FusedGaussianAdam: rows with sigmoid(opacity) < opacity_cull, or a mean
     exp(scale) below scale_cull or above scale_max are removed from the parameters and both moments (activated=True: the
@@ -224,25 +244,14 @@ def prune_gaussians(opt, opacity_cull, scale_cull, scale_max, activated=False):
     _check_opt(opt)
     soa = opt.soa
     P, dev = soa.P, soa.flat.device
-    L = _map_lib.lib()
-    ws = torch.empty(max(int(L.gs2d_map_prune_ws_bytes(P)), 4), dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        n_keep = L.gs2d_map_prune_select(P, soa.views["opacities"].data_ptr(), soa.views["scales"].data_ptr(), int(bool(activated)),
-                                         float(opacity_cull), float(scale_cull), float(scale_max), ws.data_ptr(), _stream_ptr(dev))
-    if n_keep < 0:
-        raise RuntimeError(_map_lib.last_error())
-    new = [torch.empty(BUCKET_FLOATS * n_keep, dtype=torch.float32, device=dev) for _ in range(3)]
-    src, dst, widths = [], [], []
-    for nb, ob in zip(new, (soa.flat, opt.exp_avg, opt.exp_avg_sq)):
-        for (name, nv), ov in zip(_views(nb, n_keep).items(), _views(ob, P).values()):
-            src.append(ov.data_ptr()); dst.append(nv.data_ptr()); widths.append(BUCKET_FIELDS[name])
-    n = len(src)
-    with _on_device(dev):
-        rc = L.gs2d_map_compact(P, ws.data_ptr(), n, (C.c_void_p * n)(*src), (C.c_void_p * n)(*dst), (C.c_int * n)(*widths),
-                                _stream_ptr(dev))
-    if rc < 0:
-        raise RuntimeError(_map_lib.last_error())
-    _adopt(opt, new[0], new[1], new[2], n_keep)
+    ws = torch.empty(max(int(_map_lib.lib().gs2d_map_prune_ws_bytes(P)), 4), dtype=torch.uint8, device=dev)
+    n_keep = _map_lib.call("gs2d_map_prune_select", dev, P, soa.views["opacities"].data_ptr(), soa.views["scales"].data_ptr(),
+                           int(bool(activated)), float(opacity_cull), float(scale_cull), float(scale_max), ws.data_ptr())
+    r = _Realloc(opt, n_keep)
+    n, vp = len(BUCKET_FIELDS) + r.n_mom, C.c_void_p  # the fifteen arrays: parameters, then both moments
+    _map_lib.call("gs2d_map_compact", dev, P, ws.data_ptr(), n, (vp * n)(*r.psrc, *r.msrc), (vp * n)(*r.pdst, *r.mdst),
+                  (C.c_int * n)(*BUCKET_FIELDS.values(), *r.widths))
+    r.adopt()
     return P - n_keep
 
 
@@ -329,11 +338,7 @@ class DensificationStats:
         for t, name in ((radii, "radii"), (means2D_grad, "means2D_grad")):
             _require(t.is_cuda and t.device == dev, f"{name} must be a CUDA tensor on {dev} (no CPU fallback)")
         accum, denom = self.current()
-        with _on_device(dev):
-            rc = _map_lib.lib().gs2d_map_densify_stats(P, radii.data_ptr(), means2D_grad.data_ptr(), accum.data_ptr(),
-                                                       denom.data_ptr(), _stream_ptr(dev))
-        if rc < 0:
-            raise RuntimeError(_map_lib.last_error())
+        _map_lib.call("gs2d_map_densify_stats", dev, P, radii.data_ptr(), means2D_grad.data_ptr(), accum.data_ptr(), denom.data_ptr())
 
 
 def _densify_thresholds(cfg):
@@ -369,32 +374,14 @@ def densify_and_prune(opt, stats, densify_cfg, generator=None):
     soa = opt.soa
     P, dev = soa.P, soa.flat.device
     accum, denom = stats.current()
-    L = _map_lib.lib()
-    ws = torch.empty(max(int(L.gs2d_map_densify_ws_bytes(P)), 4), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(_map_lib.lib().gs2d_map_densify_ws_bytes(P)), 4), dtype=torch.uint8, device=dev)
     noise = torch.randn((P, 2, 2), generator=generator, dtype=torch.float32, device=dev)
     counts = (C.c_uint32 * _map_lib.WS_DENSIFY_WORDS)()
-    with _on_device(dev):
-        P_new = L.gs2d_map_densify_select(P, soa.views["opacities"].data_ptr(), soa.views["scales"].data_ptr(), accum.data_ptr(),
-                                          denom.data_ptr(), T, D, opacity_cull, scale_cull, M, ws.data_ptr(), counts, _stream_ptr(dev))
-    if P_new < 0:
-        raise RuntimeError(_map_lib.last_error())
+    P_new = _map_lib.call("gs2d_map_densify_select", dev, P, soa.views["opacities"].data_ptr(), soa.views["scales"].data_ptr(),
+                          accum.data_ptr(), denom.data_ptr(), T, D, opacity_cull, scale_cull, M, ws.data_ptr(), counts)
     n_cloned, n_split = int(counts[_map_lib.WS_DENSIFY_N_CLONED]), int(counts[_map_lib.WS_DENSIFY_N_SPLIT])
-    new = [torch.empty(BUCKET_FLOATS * P_new, dtype=torch.float32, device=dev) for _ in range(3)]
-    ptrs = lambda buf, n: [v.data_ptr() for v in _views(buf, n).values()]
-    vp5, n_mom = C.c_void_p * len(BUCKET_FIELDS), 2 * len(BUCKET_FIELDS)
-    vpm = C.c_void_p * n_mom
-    with _on_device(dev):
-        rc = L.gs2d_map_densify_write(P, ws.data_ptr(), noise.data_ptr(), vp5(*ptrs(soa.flat, P)), vp5(*ptrs(new[0], P_new)), n_mom,
-                                      vpm(*(ptrs(opt.exp_avg, P) + ptrs(opt.exp_avg_sq, P))),
-                                      vpm(*(ptrs(new[1], P_new) + ptrs(new[2], P_new))),
-                                      (C.c_int * n_mom)(*(2 * list(BUCKET_FIELDS.values()))), _stream_ptr(dev))
-    if rc < 0:
-        raise RuntimeError(_map_lib.last_error())
-    # The write kernel still reads the old buffers on this stream; when they were allocated on another one, the caching
-    # allocator must not hand them out there before it has finished.
-    stream = torch.cuda.current_stream(dev)
-    for old in (soa.flat, opt.exp_avg, opt.exp_avg_sq, accum):
-        old.record_stream(stream)
-    _adopt(opt, new[0], new[1], new[2], P_new)
+    r = _Realloc(opt, P_new)
+    _map_lib.call("gs2d_map_densify_write", dev, P, ws.data_ptr(), noise.data_ptr(), r.psrc, r.pdst, r.n_mom, r.msrc, r.mdst, r.widths)
+    r.adopt(accum)
     stats.reset()
     return DensifyResult(n_cloned, n_split, P + n_cloned + n_split - P_new, P_new)

@@ -11,17 +11,15 @@ handing a finished local map to the global map.
 
 Conventions are those of densify.py.  No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError before
 anything is launched; kernels run on torch's current stream.  Not covered: SH colours, isotropic storage, exposure."""
-import ctypes as C
 from collections import OrderedDict
 
 import torch
 
 from . import _map_lib
-from .ba_shard import BUCKET_FIELDS, BUCKET_FLOATS
-from .densify import _adopt, _check_frame, _check_opt, _check_tensor, _intrinsics, _require, seed_from_frame
+from .ba_shard import BUCKET_FIELDS
+from .densify import _Realloc, _check_frame, _check_opt, _check_tensor, _intrinsics, _ptr, _require, seed_from_frame
 from .mapping import RawGaussianAdam
-from .optim import FusedGaussianAdam, GaussianSoA, _views
-from .rasterizer import _on_device, _stream_ptr
+from .optim import FusedGaussianAdam, GaussianSoA
 
 
 def create_map(gt_color, gt_depth, intrinsics, lrs, *, w2c=None, raw=True, betas=(0.9, 0.999), eps=1e-15):
@@ -98,25 +96,10 @@ def merge_local_map(opt, params, transfer, *, opacity_cap=0.01, activated=False)
         _require(params[name].is_cuda and params[name].device == dev, f"params[{name!r}] must be a CUDA tensor on {dev} (no CPU fallback)")
     _require(transfer.is_cuda and transfer.device == dev, f"transfer must be a CUDA tensor on {dev} (no CPU fallback)")
     _require(P + n <= 1 << 29, "the merged map must have at most 2^29 rows")
-    Pn = P + n
-    new = [torch.empty(BUCKET_FLOATS * Pn, dtype=torch.float32, device=dev) for _ in range(3)]
-    if Pn:
-        ptrs = lambda buf, rows: [v.data_ptr() or None for v in _views(buf, rows).values()]
-        vp5, n_mom = C.c_void_p * len(BUCKET_FIELDS), 2 * len(BUCKET_FIELDS)
-        vpm = C.c_void_p * n_mom
-        with _on_device(dev):
-            rc = _map_lib.lib().gs2d_map_merge(
-                P, n, vp5(*ptrs(soa.flat, P)), vp5(*[params[name].data_ptr() or None for name in BUCKET_FIELDS]),
-                vp5(*ptrs(new[0], Pn)), n_mom, vpm(*(ptrs(opt.exp_avg, P) + ptrs(opt.exp_avg_sq, P))),
-                vpm(*(ptrs(new[1], Pn) + ptrs(new[2], Pn))), (C.c_int * n_mom)(*(2 * list(BUCKET_FIELDS.values()))),
-                transfer.data_ptr(), cap, _stream_ptr(dev))
-        if rc < 0:
-            raise RuntimeError(_map_lib.last_error())
-        # The kernel still reads the old buffers and the incoming ones on this stream; when they were allocated on another
-        # one, the caching allocator must not hand them out there before it has finished.
-        stream = torch.cuda.current_stream(dev)
-        for old in (soa.flat, opt.exp_avg, opt.exp_avg_sq, transfer, *(params[name] for name in BUCKET_FIELDS)):
-            if old.numel():
-                old.record_stream(stream)
-    _adopt(opt, new[0], new[1], new[2], Pn)
-    return Pn
+    r = _Realloc(opt, P + n)
+    read = (transfer, *(params[name] for name in BUCKET_FIELDS)) if P + n else ()  # an empty map and nothing incoming: no launch
+    if read:
+        _map_lib.call("gs2d_map_merge", dev, P, n, r.psrc, r.vp5(*(_ptr(t) or None for t in read[1:])), r.pdst, r.n_mom, r.msrc,
+                      r.mdst, r.widths, transfer.data_ptr(), cap)
+    r.adopt(*read)
+    return P + n

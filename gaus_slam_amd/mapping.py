@@ -24,16 +24,11 @@ import torch
 
 from . import _map_lib
 from .ba_shard import BUCKET_FIELDS, GradBucket
+from .densify import _ptr, _require
 from .optim import FusedGaussianAdam
-from .rasterizer import _on_device, _stream_ptr
 
 ACT_FIELDS = OrderedDict((n, BUCKET_FIELDS[n]) for n in ("opacities", "scales", "rotations"))  # the [7P] block, in order
 ACT_FLOATS = sum(ACT_FIELDS.values())
-
-
-def _require(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
 
 
 class RawGaussianAdam(FusedGaussianAdam):
@@ -82,12 +77,8 @@ class RawGaussianAdam(FusedGaussianAdam):
         self._sync()
         soa = self.soa
         raw, act, dev = soa.views, self._act_views, soa.flat.device
-        with _on_device(dev):
-            rc = _map_lib.lib().gs2d_map_activate(soa.P, raw["opacities"].data_ptr(), raw["scales"].data_ptr(),
-                                                  raw["rotations"].data_ptr(), act["opacities"].data_ptr(),
-                                                  act["scales"].data_ptr(), act["rotations"].data_ptr(), _stream_ptr(dev))
-        if rc < 0:
-            raise RuntimeError(_map_lib.last_error())
+        _map_lib.call("gs2d_map_activate", dev, soa.P, raw["opacities"].data_ptr(), raw["scales"].data_ptr(), raw["rotations"].data_ptr(),
+                      act["opacities"].data_ptr(), act["scales"].data_ptr(), act["rotations"].data_ptr())
         self._activation += 1
         self._act_valid = True
         out = OrderedDict((n, (act[n] if n in act else raw[n]).detach().requires_grad_(True)) for n in BUCKET_FIELDS)
@@ -133,13 +124,9 @@ class RawGaussianAdam(FusedGaussianAdam):
         self._act_valid = False
         dev = soa.flat.device
         lrs = (C.c_float * len(BUCKET_FIELDS))(*self.lr)
-        with _on_device(dev):
-            rc = _map_lib.lib().gs2d_map_raw_step(soa.P, soa.flat.data_ptr(), self._act.data_ptr(), grad_flat.data_ptr(),
-                                                  self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lrs, self.betas[0],
-                                                  self.betas[1], self.eps, self.step_count,
-                                                  None if raw_grad_out is None else raw_grad_out.data_ptr(), _stream_ptr(dev))
-        if rc < 0:
-            raise RuntimeError(_map_lib.last_error())
+        _map_lib.call("gs2d_map_raw_step", dev, soa.P, soa.flat.data_ptr(), self._act.data_ptr(), grad_flat.data_ptr(),
+                      self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), lrs, self.betas[0], self.betas[1], self.eps, self.step_count,
+                      _ptr(raw_grad_out))
 
 
 def map_frames(opt, frames, num_iters, w_color, w_depth, w_dist, *, order=None, stats=None, densify_cfg=None, densify_interval=0,

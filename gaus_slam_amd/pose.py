@@ -17,8 +17,8 @@ No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError
 import torch
 
 from . import _map_lib
-from .densify import _check_tensor, _require
-from .rasterizer import _on_device, _stream_ptr
+from .densify import _check_frame, _check_tensor, _ptr, _require
+from .rasterizer import _on_device
 
 LR_KEYS = ("cam_rot_lr_init", "cam_rot_lr_final", "cam_rot_lr_max_step", "cam_trans_lr_init", "cam_trans_lr_final",
            "cam_trans_lr_max_step")
@@ -86,12 +86,7 @@ class PoseOptimizer:
         self._state = torch.empty(_map_lib.POSE_STATE_WORDS, dtype=torch.int32, device=device)
         self.w2c = torch.empty((4, 4), dtype=torch.float32, device=device).requires_grad_(True)
         self._pending, self._free, self._last = [], [], None
-        p = lambda t: None if t is None else t.data_ptr()
-        with _on_device(device):
-            rc = _map_lib.lib().gs2d_pose_init(self._state.data_ptr(), p(initial_w2c), p(left), self.w2c.data_ptr(),
-                                               _stream_ptr(device))
-        if rc < 0:
-            raise RuntimeError(_map_lib.last_error())
+        _map_lib.call("gs2d_pose_init", device, self._state.data_ptr(), _ptr(initial_w2c), _ptr(left), self.w2c.data_ptr())
 
     def zero_grad(self):
         self.w2c.grad = None
@@ -116,12 +111,8 @@ class PoseOptimizer:
         for m, name in ((left, "left"), (next_left, "next_left")):
             if m is not None:
                 _check_matrix(m, name, dev)
-        p = lambda t: None if t is None else t.data_ptr()
-        with _on_device(dev):
-            rc = _map_lib.lib().gs2d_pose_step(self._state.data_ptr(), grad.data_ptr(), p(left), p(next_left), self.cfg,
-                                               self.w2c.data_ptr(), _stream_ptr(dev))
-        if rc < 0:
-            raise RuntimeError(_map_lib.last_error())
+        _map_lib.call("gs2d_pose_step", dev, self._state.data_ptr(), grad.data_ptr(), _ptr(left), _ptr(next_left), self.cfg,
+                      self.w2c.data_ptr())
         self.left = left if next_left is None else next_left  # what .w2c is composed with now (unless latched)
 
     def load(self, q, t):
@@ -219,15 +210,10 @@ def frame_stats(allmap, gt_depth, *, use_weight_norm=True, eps=1e-6, depth_near=
       [1] the number of pixels in that mask                            }
       [2] the number of pixels with alpha < alpha_key                    Frontend.py:186-188: keyframe when [2] > numel * tau_k
     with d the weight-normalised, near / far-zeroed depth of render/__init__.py:46-49."""
-    from .densify import _check_frame
     W, H = _check_frame(allmap, None, gt_depth)
     dev = allmap.device
     ws = torch.empty(_map_lib.POSE_STATS_WS_DOUBLES, dtype=torch.float64, device=dev)
     out = torch.empty(3, dtype=torch.float64, device=dev)
-    with _on_device(dev):
-        rc = _map_lib.lib().gs2d_pose_frame_stats(W, H, allmap.data_ptr(), gt_depth.data_ptr(), int(bool(use_weight_norm)),
-                                                  float(eps), float(depth_near), float(depth_far), float(alpha_track),
-                                                  float(gt_min), float(alpha_key), ws.data_ptr(), out.data_ptr(), _stream_ptr(dev))
-    if rc < 0:
-        raise RuntimeError(_map_lib.last_error())
+    _map_lib.call("gs2d_pose_frame_stats", dev, W, H, allmap.data_ptr(), gt_depth.data_ptr(), int(bool(use_weight_norm)), float(eps),
+                  float(depth_near), float(depth_far), float(alpha_track), float(gt_min), float(alpha_key), ws.data_ptr(), out.data_ptr())
     return out
