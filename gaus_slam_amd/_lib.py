@@ -3,9 +3,9 @@ there is no CPU fallback anywhere in this package."""
 import ctypes as C
 import os
 
-from . import build as _build
+from . import _host, build as _build
 
-ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
+ALLOC_FN = _host.ALLOC_FN  # gs2d_alloc_fn: one type object, so the allocator callback _host creates matches argtypes below
 
 EXPORTS = ["gs2d_forward", "gs2d_backward", "gs2d_forward_posed", "gs2d_backward_posed", "gs2d_mark_visible", "sknn_dist2", "gs2d_geometry_bytes",
            "gs2d_image_bytes", "gs2d_binning_bytes", "gs2d_geometry_layout", "gs2d_binning_layout",
@@ -105,6 +105,12 @@ def lib():
 
 def last_error():
     return lib().gs2d_last_error().decode()
+
+
+def call(name, device, *args, error=None):
+    """_host.call on this library: `error` is the text to raise for the entries that set none (gs2d_slam_loss,
+    gs2d_adam_step, sknn_dist2)."""
+    return _host.call(lib(), last_error, name, device, *args, error=error)
 
 
 def build_info():

@@ -3,8 +3,7 @@ libgs2d_map_hip.so.  Like _lib.py it fails loudly when the library is missing: t
 import ctypes as C
 import os
 
-from . import build as _build
-from .rasterizer import _on_device, _stream_ptr
+from . import _host, build as _build
 
 EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_select", "gs2d_map_seed_write",
            "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_densify_stats", "gs2d_map_densify_ws_bytes",
@@ -87,11 +86,7 @@ def last_error():
 def call(name, device, *args):
     """Entry point `name` of the library with `args` and, as its last argument, torch's current stream on `device`, with that
     device current.  Returns what it returns (a count, or 0); a negative return raises RuntimeError with the library's text."""
-    with _on_device(device):
-        rc = getattr(lib(), name)(*args, _stream_ptr(device))
-    if rc < 0:
-        raise RuntimeError(last_error())
-    return rc
+    return _host.call(lib(), last_error, name, device, *args)
 
 
 def build_info():

@@ -28,6 +28,7 @@ from collections import OrderedDict, namedtuple
 import torch
 
 from . import _map_lib
+from ._host import ptr as _ptr  # noqa: F401  (pose.py, mapping.py and localmap.py take it from here)
 from .ba_shard import BUCKET_FIELDS, BUCKET_FLOATS
 from .optim import _views
 
@@ -91,10 +92,6 @@ def c2w_from_w2c(w2c):
     _require(isinstance(w2c, torch.Tensor) and tuple(w2c.shape) == (4, 4), "w2c must be a [4,4] tensor")
     _require(w2c.is_cuda, "w2c must be a CUDA tensor (no CPU fallback)")
     return torch.linalg.inv(w2c.detach().float()).contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def seed_select(allmap, gt_depth, *, mode="splatam", sil_thres=None, edge_thres=0.4, use_weight_norm=True, eps=1e-6,

@@ -1,11 +1,9 @@
 """simple_knn.distCUDA2 host wrapper: mean squared distance to the 3 nearest other points (call sites
 scene/Gaussians.py:77,218 of the reference).  Compute is the HIP kernel set in csrc/sknn.hip."""
-import ctypes as C
-
 import torch
 
 from . import _lib
-from .rasterizer import _Chunk
+from ._host import chunks
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:
@@ -18,11 +16,6 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     out = torch.zeros((N,), dtype=torch.float32, device=pts.device)
     if N == 0:
         return out
-    ws = _Chunk(pts.device)
-    with torch.cuda.device(pts.device):
-        rc = _lib.lib().sknn_dist2(N, pts.data_ptr(), out.data_ptr(), ws.cb, ws.user,
-                                   C.c_void_p(torch.cuda.current_stream(pts.device).cuda_stream))
-    ws.release()
-    if rc < 0:
-        raise RuntimeError("sknn_dist2 failed: " + _lib.last_error())
+    with chunks(pts.device, 1) as (ws,):
+        _lib.call("sknn_dist2", pts.device, N, pts.data_ptr(), out.data_ptr(), ws.cb, ws.user, error="sknn_dist2 failed")
     return out

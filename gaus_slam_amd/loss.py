@@ -8,23 +8,34 @@ One autograd node, two HIP kernels (csrc/gs2d_loss.hip).  Settings outside the d
 import torch
 
 from . import _lib
-from .rasterizer import _on_device, _stream_ptr
+from ._host import ptr
 
 _WS_DOUBLES = 2560  # GS2D_LOSS_WS_DOUBLES (include/gs2d_rasterizer.h)
 
 
 def _call(cfg, W, H, color_, allmap_, gtc, gtd, ws, out, g_color, g_allmap, upstream, dev):
-    p = lambda t: None if t is None else t.data_ptr()
-    with _on_device(dev):
-        rc = _lib.lib().gs2d_slam_loss(
-            int(cfg["mode"]), W, H, color_.data_ptr(), allmap_.data_ptr(), gtc.data_ptr(), gtd.data_ptr(),
-            float(cfg["w_color"]), float(cfg["w_depth"]), float(cfg.get("w_dist", 0.0)), float(cfg.get("silmask_th", 0.9)),
-            float(cfg.get("edge_thres", 0.4)), int(bool(cfg.get("use_edge_growth", False))),
-            int(bool(cfg.get("use_weight_norm", True))), float(cfg.get("eps", 1e-6)), float(cfg.get("depth_near", 1e-2)),
-            float(cfg.get("depth_far", 1e2)), ws.data_ptr(), p(out), p(g_color), p(g_allmap), p(upstream),
-            _stream_ptr(dev))
-    if rc < 0:
-        raise RuntimeError("gs2d_slam_loss failed")
+    _lib.call(
+        "gs2d_slam_loss", dev, int(cfg["mode"]), W, H, color_.data_ptr(), allmap_.data_ptr(), gtc.data_ptr(), gtd.data_ptr(),
+        float(cfg["w_color"]), float(cfg["w_depth"]), float(cfg.get("w_dist", 0.0)), float(cfg.get("silmask_th", 0.9)),
+        float(cfg.get("edge_thres", 0.4)), int(bool(cfg.get("use_edge_growth", False))),
+        int(bool(cfg.get("use_weight_norm", True))), float(cfg.get("eps", 1e-6)), float(cfg.get("depth_near", 1e-2)),
+        float(cfg.get("depth_far", 1e2)), ws.data_ptr(), ptr(out), ptr(g_color), ptr(g_allmap), ptr(upstream),
+        error="gs2d_slam_loss failed")
+
+
+def _prepare(color, allmap, gt_color, gt_depth):
+    """The contiguous float32 inputs of a loss call, its workspace and its [8] term vector:
+    (color_, allmap_, gtc [H,W,3], gtd [H,W], ws, out, W, H, dev)."""
+    if not color.is_cuda:
+        raise RuntimeError("color must be a CUDA tensor")
+    dev = color.device
+    H, W = color.shape[1], color.shape[2]
+    color_, allmap_ = color.detach().float().contiguous(), allmap.detach().float().contiguous()
+    gtc = gt_color.detach().float().contiguous().reshape(H, W, 3)
+    gtd = gt_depth.detach().float().contiguous().reshape(H, W)
+    ws = torch.empty(_WS_DOUBLES, dtype=torch.float64, device=dev)
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    return color_, allmap_, gtc, gtd, ws, out, W, H, dev
 
 
 class _SlamLoss(torch.autograd.Function):
@@ -33,15 +44,7 @@ class _SlamLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, color, allmap, gt_color, gt_depth, cfg):
-        if not color.is_cuda:
-            raise RuntimeError("color must be a CUDA tensor")
-        dev = color.device
-        H, W = color.shape[1], color.shape[2]
-        color_, allmap_ = color.detach().float().contiguous(), allmap.detach().float().contiguous()
-        gtc = gt_color.detach().float().contiguous().reshape(H, W, 3)
-        gtd = gt_depth.detach().float().contiguous().reshape(H, W)
-        ws = torch.empty(_WS_DOUBLES, dtype=torch.float64, device=dev)
-        out = torch.empty(8, dtype=torch.float32, device=dev)
+        color_, allmap_, gtc, gtd, ws, out, W, H, dev = _prepare(color, allmap, gt_color, gt_depth)
         _call(cfg, W, H, color_, allmap_, gtc, gtd, ws, out, None, None, None, dev)
         ctx.save_for_backward(color_, allmap_, gtc, gtd, ws)
         ctx.cfg = cfg
@@ -60,18 +63,20 @@ class _SlamLoss(torch.autograd.Function):
 
 
 def _loss_and_grads(color, allmap, gt_color, gt_depth, cfg):
-    if not color.is_cuda:
-        raise RuntimeError("color must be a CUDA tensor")
-    dev = color.device
-    H, W = color.shape[1], color.shape[2]
-    color_, allmap_ = color.detach().float().contiguous(), allmap.detach().float().contiguous()
-    gtc = gt_color.detach().float().contiguous().reshape(H, W, 3)
-    gtd = gt_depth.detach().float().contiguous().reshape(H, W)
-    ws = torch.empty(_WS_DOUBLES, dtype=torch.float64, device=dev)
-    out = torch.empty(8, dtype=torch.float32, device=dev)
+    color_, allmap_, gtc, gtd, ws, out, W, H, dev = _prepare(color, allmap, gt_color, gt_depth)
     g_color, g_allmap = torch.empty_like(color_), torch.empty_like(allmap_)
     _call(cfg, W, H, color_, allmap_, gtc, gtd, ws, out, g_color, g_allmap, None, dev)
     return out[0], g_color, g_allmap
+
+
+def _tracking_cfg(w_color, w_depth, silmask_th, use_weight_norm, eps, depth_near, depth_far):
+    return dict(mode=0, w_color=w_color, w_depth=w_depth, silmask_th=silmask_th, use_weight_norm=use_weight_norm, eps=eps,
+                depth_near=depth_near, depth_far=depth_far)
+
+
+def _mapping_cfg(w_color, w_depth, w_dist, use_edge_growth, edge_thres, use_weight_norm, eps, depth_near, depth_far):
+    return dict(mode=1, w_color=w_color, w_depth=w_depth, w_dist=w_dist, use_edge_growth=use_edge_growth, edge_thres=edge_thres,
+                use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
 
 
 def tracking_loss_and_grads(color, allmap, gt_color, gt_depth, w_color, w_depth, silmask_th=0.9, use_weight_norm=True, eps=1e-6,
@@ -82,30 +87,26 @@ def tracking_loss_and_grads(color, allmap, gt_color, gt_depth, w_color, w_depth,
         loss, g_color, g_allmap = tracking_loss_and_grads(pkg["render_color"], pkg["allmap"], ...)
         torch.autograd.backward([pkg["render_color"], pkg["allmap"]], [g_color, g_allmap])
     Returns (loss, dL_dcolor [3, H, W], dL_dallmap [7, H, W]); the values equal tracking_loss(...) and its .backward()."""
-    return _loss_and_grads(color, allmap, gt_color, gt_depth, dict(
-        mode=0, w_color=w_color, w_depth=w_depth, silmask_th=silmask_th, use_weight_norm=use_weight_norm, eps=eps,
-        depth_near=depth_near, depth_far=depth_far))
+    return _loss_and_grads(color, allmap, gt_color, gt_depth,
+                           _tracking_cfg(w_color, w_depth, silmask_th, use_weight_norm, eps, depth_near, depth_far))
 
 
 def mapping_loss_and_grads(color, allmap, gt_color, gt_depth, w_color, w_depth, w_dist, use_edge_growth=False, edge_thres=0.4,
                            use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2):
     """mapping_loss and its gradients in one call (see tracking_loss_and_grads)."""
-    return _loss_and_grads(color, allmap, gt_color, gt_depth, dict(
-        mode=1, w_color=w_color, w_depth=w_depth, w_dist=w_dist, use_edge_growth=use_edge_growth, edge_thres=edge_thres,
-        use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far))
+    return _loss_and_grads(color, allmap, gt_color, gt_depth, _mapping_cfg(
+        w_color, w_depth, w_dist, use_edge_growth, edge_thres, use_weight_norm, eps, depth_near, depth_far))
 
 
 def tracking_loss(color, allmap, gt_color, gt_depth, w_color, w_depth, silmask_th=0.9, use_weight_norm=True, eps=1e-6,
                   depth_near=1e-2, depth_far=1e2):
     """slam/Loss.py:35-49 on top of render/__init__.py:46-49: masked (depth-valid & alpha > silmask_th) L1 SUMS."""
-    return _SlamLoss.apply(color, allmap, gt_color, gt_depth, dict(
-        mode=0, w_color=w_color, w_depth=w_depth, silmask_th=silmask_th, use_weight_norm=use_weight_norm, eps=eps,
-        depth_near=depth_near, depth_far=depth_far))
+    return _SlamLoss.apply(color, allmap, gt_color, gt_depth,
+                           _tracking_cfg(w_color, w_depth, silmask_th, use_weight_norm, eps, depth_near, depth_far))
 
 
 def mapping_loss(color, allmap, gt_color, gt_depth, w_color, w_depth, w_dist, use_edge_growth=False, edge_thres=0.4,
                  use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2):
     """slam/Loss.py:51-58: masked L1 MEANS for colour / depth plus the mean of render_dist over the colour mask."""
-    return _SlamLoss.apply(color, allmap, gt_color, gt_depth, dict(
-        mode=1, w_color=w_color, w_depth=w_depth, w_dist=w_dist, use_edge_growth=use_edge_growth, edge_thres=edge_thres,
-        use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far))
+    return _SlamLoss.apply(color, allmap, gt_color, gt_depth, _mapping_cfg(
+        w_color, w_depth, w_dist, use_edge_growth, edge_thres, use_weight_norm, eps, depth_near, depth_far))

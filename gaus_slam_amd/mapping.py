@@ -25,7 +25,7 @@ import torch
 from . import _map_lib
 from .ba_shard import BUCKET_FIELDS, GradBucket
 from .densify import _ptr, _require
-from .optim import FusedGaussianAdam
+from .optim import FusedGaussianAdam, _views
 
 ACT_FIELDS = OrderedDict((n, BUCKET_FIELDS[n]) for n in ("opacities", "scales", "rotations"))  # the [7P] block, in order
 ACT_FLOATS = sum(ACT_FIELDS.values())
@@ -55,10 +55,7 @@ class RawGaussianAdam(FusedGaussianAdam):
         if self._generation != soa.generation or self._act.numel() != ACT_FLOATS * soa.P:
             P, dev = soa.P, soa.flat.device
             self._act = torch.empty(ACT_FLOATS * P, dtype=torch.float32, device=dev)
-            self._act_views, o = OrderedDict(), 0
-            for name, k in ACT_FIELDS.items():
-                self._act_views[name] = self._act[o:o + k * P].view(P, k)
-                o += k * P
+            self._act_views = _views(self._act, P, ACT_FIELDS)
             self._bucket = GradBucket(P, dev)
             self._generation = soa.generation
             self._act_valid = False

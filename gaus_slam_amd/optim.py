@@ -14,7 +14,6 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .rasterizer import _on_device, _stream_ptr
 from .ba_shard import BUCKET_FIELDS, BUCKET_FLOATS
 
 # reference name (optimizer group "name", scene/Gaussians.py:124-135) for each bucket field
@@ -22,9 +21,10 @@ GROUP_NAMES = OrderedDict([("means3D", "xyz"), ("opacities", "opacity"), ("scale
                            ("colors", "rgb")])
 
 
-def _views(flat, P):
+def _views(flat, P, fields=BUCKET_FIELDS):
+    """Per-field [P,k] views of a flat buffer that holds the fields one after the other."""
     out, o = OrderedDict(), 0
-    for name, k in BUCKET_FIELDS.items():
+    for name, k in fields.items():
         out[name] = flat[o:o + k * P].view(P, k)
         o += k * P
     return out
@@ -96,12 +96,9 @@ class FusedGaussianAdam:
         n = len(BUCKET_FIELDS)
         ends = (C.c_ulonglong * n)(*self._group_end())
         lrs = (C.c_float * n)(*self.lr)
-        with _on_device(soa.flat.device):
-            rc = _lib.lib().gs2d_adam_step(n, ends, lrs, self.betas[0], self.betas[1], self.eps, self.step_count,
-                                           soa.flat.numel(), soa.flat.data_ptr(), grad_flat.data_ptr(), self.exp_avg.data_ptr(),
-                                           self.exp_avg_sq.data_ptr(), _stream_ptr(soa.flat.device))
-        if rc != 0:
-            raise RuntimeError("gs2d_adam_step failed (bad group table or misaligned buffers)")
+        _lib.call("gs2d_adam_step", soa.flat.device, n, ends, lrs, self.betas[0], self.betas[1], self.eps, self.step_count,
+                  soa.flat.numel(), soa.flat.data_ptr(), grad_flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                  error="gs2d_adam_step failed (bad group table or misaligned buffers)")
 
     # -- topology changes keep parameters and moments aligned (scene/Gaussians.py:143-184) --------------------------
     def _rebuild(self, new_fields, new_m, new_v):

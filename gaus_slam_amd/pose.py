@@ -17,8 +17,8 @@ No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError
 import torch
 
 from . import _map_lib
+from ._host import on_device as _on_device
 from .densify import _check_frame, _check_tensor, _ptr, _require
-from .rasterizer import _on_device
 
 LR_KEYS = ("cam_rot_lr_init", "cam_rot_lr_final", "cam_rot_lr_max_step", "cam_trans_lr_init", "cam_trans_lr_final",
            "cam_trans_lr_max_step")

@@ -9,23 +9,18 @@ it runs unchanged on PyTorch-ROCm.  All compute happens in the HIP library behin
 """
 import contextlib
 import ctypes as C
-import itertools
 from typing import NamedTuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._host import Chunk as _Chunk, chunks as _chunks, on_device as _on_device, ptr as _ptr, stream_ptr as _stream_ptr  # noqa: F401
 
 NUM_CHANNELS = 3
-
-
-def _ptr(t):
-    """Device pointer or NULL for empty tensors (the reference relies on empty tensors having a null data pointer,
-    rasterizer_impl.cu:327-328)."""
-    if t is None or t.numel() == 0:
-        return None
-    return t.data_ptr()
+# gs2d_backward_staged's `stages` (include/gs2d_rasterizer.h): GS2D_BWD_BLEND, GS2D_BWD_PREPROCESS, and both with
+# GS2D_BWD_POSE_4X4 (1|2|4: all sixteen floats of a [4,4] pose gradient are written)
+_BWD_BLEND, _BWD_PREPROCESS, _BWD_POSE_ONLY = 1, 2, 7
 
 
 def _check_cuda(t, name):
@@ -34,64 +29,28 @@ def _check_cuda(t, name):
 
 
 def _f32c(t):
+    if t is None:
+        return None
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
 
 
-class _Chunk:
-    """Allocator callback target: the C side asks for N bytes, we hand out a torch uint8 tensor (the resizeFunctional
-    lambda of rasterize_points.cu:31-37).  ONE ctypes callback exists per process (creating CFUNCTYPE objects per call
-    costs tens of microseconds); the `user` pointer the C side passes back selects the live _Chunk."""
-
-    _live = {}
-    _next = itertools.count(1)  # next() on a count is atomic under the GIL: concurrent host threads never share a key
-
-    def __init__(self, device):
-        self.device = device
-        self.tensor = torch.empty(0, dtype=torch.uint8, device=device)
-        self.key = next(_Chunk._next)
-        _Chunk._live[self.key] = self
-        self.cb = _CHUNK_CB
-        self.user = C.c_void_p(self.key)
-
-    def release(self):
-        _Chunk._live.pop(self.key, None)
+def _check_forward_inputs(means3D, inputs):
+    """The reference's shape and CHECK_INPUT errors of a forward; inputs: (name, tensor) pairs."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    for name, t in inputs:
+        _check_cuda(t, name)
 
 
-def _chunk_alloc(user, nbytes):
-    ch = _Chunk._live[int(user)]
-    ch.tensor = torch.empty(int(nbytes), dtype=torch.uint8, device=ch.device)
-    return ch.tensor.data_ptr()
-
-
-_CHUNK_CB = _lib.ALLOC_FN(_chunk_alloc)
-
-
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream_ptr(device):
-    """Raw hipStream_t of torch's current stream on `device` (fast path: no Stream object is built)."""
-    if _RAW_STREAM is not None:
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        return C.c_void_p(_RAW_STREAM(idx))
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-class _on_device:
-    """`with torch.cuda.device(dev)` that costs nothing when `dev` already is the current device (the usual case)."""
-
-    def __init__(self, device):
-        idx = device.index
-        self.ctx = None if idx is None or idx == torch.cuda.current_device() else torch.cuda.device(device)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            return self.ctx.__exit__(*exc)
-        return False
+def _forward_outputs(means3D, H, W, lead=()):
+    """(P, device, out_color [*lead,3,H,W], out_others [*lead,7,H,W], radii [*lead,P]) of a forward; lead: () or (K,)."""
+    dev = means3D.device
+    P = means3D.size(0)
+    # P == 0 returns zero images (rasterize_points.cu:100-101); otherwise the kernels write every output element,
+    # so no fill kernels are spent on them.
+    alloc = torch.zeros if P == 0 else torch.empty
+    return (P, dev, alloc(lead + (NUM_CHANNELS, H, W), dtype=torch.float32, device=dev),
+            alloc(lead + (7, H, W), dtype=torch.float32, device=dev), alloc(lead + (P,), dtype=torch.int32, device=dev))
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, transMat_precomp,
@@ -100,44 +59,56 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     """_C.rasterize_gaussians (rasterize_points.cu:39-138): returns
     (num_rendered, out_color[3,H,W], out_others[7,H,W], radii[P], geomBuffer, binningBuffer, imgBuffer).
     pose_Rt [3,4] / pose_quat [4] (extension, see gs2d_forward_posed): rigid transform fused into the preprocess."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    for name, t in (("background", background), ("means3D", means3D), ("colors", colors), ("opacity", opacity),
-                    ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
-                    ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh), ("campos", campos)):
-        _check_cuda(t, name)
-    L = _lib.lib()
-    dev = means3D.device
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-    # P == 0 returns zero images (rasterize_points.cu:100-101); otherwise the kernels write every output element,
-    # so no fill kernels are spent on them.
-    alloc = torch.zeros if P == 0 else torch.empty
-    out_color = alloc((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
-    out_others = alloc((7, H, W), dtype=torch.float32, device=dev)
-    radii = alloc((P,), dtype=torch.int32, device=dev)
-    geom, binning, img = _Chunk(dev), _Chunk(dev), _Chunk(dev)
+    _check_forward_inputs(means3D, (
+        ("background", background), ("means3D", means3D), ("colors", colors), ("opacity", opacity), ("scales", scales),
+        ("rotations", rotations), ("transMat_precomp", transMat_precomp), ("viewmatrix", viewmatrix),
+        ("projmatrix", projmatrix), ("sh", sh), ("campos", campos)))
+    H, W = int(image_height), int(image_width)
+    P, dev, out_color, out_others, radii = _forward_outputs(means3D, H, W)
     rendered = 0
-    try:
+    with _chunks(dev, 3) as (geom, binning, img):  # released before a failing call's error leaves this function
         if P != 0:
             M = sh.size(1) if sh.size(0) != 0 else 0
             keep = [_f32c(t) for t in (background, means3D, sh, colors, opacity, scales, rotations, transMat_precomp,
-                                       viewmatrix, projmatrix, campos)]
-            bg_, m3_, sh_, col_, op_, sc_, rot_, tm_, vm_, pm_, cp_ = keep
-            with _on_device(dev):
-                prt_ = _f32c(pose_Rt) if pose_Rt is not None else None
-                pq_ = _f32c(pose_quat) if pose_quat is not None else None
-                rendered = L.gs2d_forward_posed(
-                    geom.cb, geom.user, binning.cb, binning.user, img.cb, img.user, P, int(degree), M, _ptr(bg_), W, H,
-                    _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(op_), _ptr(sc_), float(scale_modifier), _ptr(rot_), _ptr(tm_),
-                    _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-                    out_color.data_ptr(), out_others.data_ptr(), radii.data_ptr(), int(bool(use_sa)), int(bool(debug)),
-                    _ptr(prt_), _ptr(pq_), _stream_ptr(dev))
-    finally:  # the callback registry never keeps a chunk of a call that raised
-        for ch in (geom, binning, img):
-            ch.release()
-    if rendered < 0:
-        raise RuntimeError(_lib.last_error())
+                                       viewmatrix, projmatrix, campos, pose_Rt, pose_quat)]
+            bg_, m3_, sh_, col_, op_, sc_, rot_, tm_, vm_, pm_, cp_, prt_, pq_ = keep
+            rendered = _lib.call(
+                "gs2d_forward_posed", dev,
+                geom.cb, geom.user, binning.cb, binning.user, img.cb, img.user, P, int(degree), M, _ptr(bg_), W, H,
+                _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(op_), _ptr(sc_), float(scale_modifier), _ptr(rot_), _ptr(tm_),
+                _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
+                out_color.data_ptr(), out_others.data_ptr(), radii.data_ptr(), int(bool(use_sa)), int(bool(debug)),
+                _ptr(prt_), _ptr(pq_))
     return rendered, out_color, out_others, radii, geom.tensor, binning.tensor, img.tensor
+
+
+# the nine gradient outputs in the order of the C ABI, and where a grad_sink entry may take an output's place (in the
+# order the entries are validated)
+_MEANS2D, _NORMAL, _OPACITIES, _COLORS, _MEANS3D, _TRANSMAT, _SH, _SCALES, _ROTATIONS = range(9)
+_SINKABLE = (("means3D", _MEANS3D), ("colors", _COLORS), ("opacities", _OPACITIES), ("scales", _SCALES), ("rotations", _ROTATIONS))
+
+
+def _grad_outputs(P, M, dev, lean, has_transmat, sink):
+    """The nine gradient tensors of one frame, in the order of the C ABI (the kernels write every element, zeros for culled
+    Gaussians: no torch.zeros fills needed).  lean: no dL_dnormal and, without a cov3D_precomp, no dL_dtransMat (None).
+    sink: see rasterize_gaussians_backward."""
+    z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    o = [z(P, 3), None if lean else z(P, 3), z(P, 1), z(P, NUM_CHANNELS), z(P, 3),
+         None if lean and not has_transmat else z(P, 9), z(P, M, 3), z(P, 2), z(P, 4)]
+    if sink:
+        for name, i in _SINKABLE:
+            s = sink.get(name)
+            if s is None:
+                continue
+            if s.shape != o[i].shape or s.dtype != torch.float32 or s.device != dev or not s.is_contiguous():
+                raise RuntimeError(f"grad_sink[{name!r}] must be a contiguous fp32 {tuple(o[i].shape)} tensor on {dev}")
+            o[i] = s.detach()  # fresh tensor object on the same memory, so autograd can adopt it as .grad without a copy
+    return o
+
+
+def _returned_grads(o):
+    """(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations)."""
+    return o[_MEANS2D], o[_COLORS], o[_OPACITIES], o[_MEANS3D], o[_TRANSMAT], o[_SH], o[_SCALES], o[_ROTATIONS]
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -164,87 +135,53 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                     ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh), ("campos", campos),
                     ("binningBuffer", binningBuffer), ("imageBuffer", imageBuffer), ("geomBuffer", geomBuffer)):
         _check_cuda(t, name)
-    L = _lib.lib()
     dev = means3D.device
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
     M = sh.size(1) if sh.size(0) != 0 else 0
-    if pose_only_out is not None:
+    pose_only = pose_only_out is not None
+    if pose_only:
         if pose_Rt is None or M != 0:
             raise RuntimeError("pose_only_out needs a pose and colors_precomp")
-        if P != 0:
-            keep = [_f32c(t) for t in (background, means3D, colors, scales, rotations, viewmatrix, projmatrix, campos,
-                                       dL_dout_color, dL_dout_others, pose_Rt)]
-            bg_, m3_, col_, sc_, rot_, vm_, pm_, cp_, dc_, do_, prt_ = keep
-            pq_ = _f32c(pose_quat) if pose_quat is not None else None  # None: the kernels derive q_cam from pose_Rt
-            with _on_device(dev):
-                # stages 1|2|4 (GS2D_BWD_POSE_4X4): all sixteen floats of pose_only_out are written
-                rc = L.gs2d_backward_staged(
-                    7, 0, P, P, int(degree), 0, int(R), _ptr(bg_), W, H, _ptr(m3_), None, _ptr(col_), _ptr(sc_), float(scale_modifier),
-                    _ptr(rot_), None, _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx), float(tan_fovy),
-                    radii.contiguous().data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), dc_.data_ptr(),
-                    do_.data_ptr(), None, None, None, None, None, None, None, None, None, int(bool(use_sa)), int(bool(debug)),
-                    _ptr(prt_), _ptr(pq_), pose_only_out.data_ptr(), _stream_ptr(dev))
-            if rc < 0:
-                raise RuntimeError(_lib.last_error())
-        else:
+        if P == 0:
             pose_only_out.zero_()
-        return pose_only_out
-    # the backward kernels write every element (zeros for culled Gaussians): no torch.zeros fills needed
-    z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dnormal = z(P, 3), z(P, 3), z(P, NUM_CHANNELS), z(P, 3)
-    dL_dopacity, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations = z(P, 1), z(P, 9), z(P, M, 3), z(P, 2), z(P, 4)
-    if lean:
-        dL_dnormal = None
-        if transMat_precomp.numel() == 0:
-            dL_dtransMat = None
-    if grad_sink:
-        def sunk(name, t):
-            s = grad_sink.get(name)
-            if s is None:
-                return t
-            if s.shape != t.shape or s.dtype != torch.float32 or s.device != dev or not s.is_contiguous():
-                raise RuntimeError(f"grad_sink[{name!r}] must be a contiguous fp32 {tuple(t.shape)} tensor on {dev}")
-            return s.detach()  # fresh tensor object on the same memory, so autograd can adopt it as .grad without a copy
-        dL_dmeans3D, dL_dcolors, dL_dopacity = sunk("means3D", dL_dmeans3D), sunk("colors", dL_dcolors), sunk("opacities", dL_dopacity)
-        dL_dscales, dL_drotations = sunk("scales", dL_dscales), sunk("rotations", dL_drotations)
+            return pose_only_out
+        sh = transMat_precomp = None  # with every per-Gaussian output: not read, not written
+        outs = (None,) * 9
+    else:
+        outs = _grad_outputs(P, M, dev, lean, transMat_precomp.numel() != 0, grad_sink)
+    dL_dpose = None
     if P != 0:
         keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, transMat_precomp, viewmatrix,
-                                   projmatrix, campos, dL_dout_color, dL_dout_others)]
-        bg_, m3_, sh_, col_, sc_, rot_, tm_, vm_, pm_, cp_, dc_, do_ = keep
+                                   projmatrix, campos, dL_dout_color, dL_dout_others, pose_Rt, pose_quat)]
+        bg_, m3_, sh_, col_, sc_, rot_, tm_, vm_, pm_, cp_, dc_, do_, prt_, pq_ = keep  # pq_ None: the kernels derive q_cam from pose_Rt
         radii_ = radii.contiguous()
-        with _on_device(dev):
-            prt_ = _f32c(pose_Rt) if pose_Rt is not None else None
-            pq_ = _f32c(pose_quat) if pose_quat is not None else None
-            dL_dpose = torch.empty((3, 4), dtype=torch.float32, device=dev) if pose_Rt is not None else None
-            tail = (P, int(degree), M, int(R), _ptr(bg_), W, H, _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(sc_),
-                    float(scale_modifier), _ptr(rot_), _ptr(tm_), _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx),
-                    float(tan_fovy), radii_.data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
-                    dc_.data_ptr(), do_.data_ptr(), dL_dmeans2D.data_ptr(), _ptr(dL_dnormal), dL_dopacity.data_ptr(),
-                    dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), _ptr(dL_dtransMat), _ptr(dL_dsh),
-                    dL_dscales.data_ptr(), dL_drotations.data_ptr(), int(bool(use_sa)), int(bool(debug)), _ptr(prt_),
-                    _ptr(pq_), _ptr(dL_dpose), _stream_ptr(dev))
-            if on_chunk is None:
-                rc = L.gs2d_backward_posed(*tail)
-            else:
-                rows = max(1, int(chunk_rows or P))
-                rc = L.gs2d_backward_staged(1, 0, 0, *tail)  # GS2D_BWD_BLEND
-                g0 = 0
-                while rc >= 0 and g0 < P:
+        if pose_only:
+            dL_dpose = pose_only_out
+        elif pose_Rt is not None:
+            dL_dpose = torch.empty((3, 4), dtype=torch.float32, device=dev)
+        tail = (P, int(degree), M, int(R), _ptr(bg_), W, H, _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(sc_),
+                float(scale_modifier), _ptr(rot_), _ptr(tm_), _ptr(vm_), _ptr(pm_), _ptr(cp_), float(tan_fovx),
+                float(tan_fovy), radii_.data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+                dc_.data_ptr(), do_.data_ptr(), *map(_ptr, outs), int(bool(use_sa)), int(bool(debug)), _ptr(prt_),
+                _ptr(pq_), _ptr(dL_dpose))
+        if pose_only:
+            _lib.call("gs2d_backward_staged", dev, _BWD_POSE_ONLY, 0, P, *tail)
+        elif on_chunk is None:
+            _lib.call("gs2d_backward_posed", dev, *tail)
+        else:
+            rows = max(1, int(chunk_rows or P))
+            with _on_device(dev):  # on_chunk runs with the device current, too
+                _lib.call("gs2d_backward_staged", dev, _BWD_BLEND, 0, 0, *tail)
+                for g0 in range(0, P, rows):
                     g1 = min(P, g0 + rows)
-                    rc = L.gs2d_backward_staged(2, g0, g1, *tail)  # GS2D_BWD_PREPROCESS on [g0, g1)
-                    if rc >= 0:
-                        on_chunk(g0, g1)
-                    g0 = g1
-        if rc < 0:
-            raise RuntimeError(_lib.last_error())
-        if pose_Rt is not None:
-            return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations,
-                    dL_dpose)
+                    _lib.call("gs2d_backward_staged", dev, _BWD_PREPROCESS, g0, g1, *tail)  # on [g0, g1)
+                    on_chunk(g0, g1)
     elif pose_Rt is not None:
-        return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations,
-                torch.zeros((3, 4), dtype=torch.float32, device=dev))
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations
+        dL_dpose = torch.zeros((3, 4), dtype=torch.float32, device=dev)
+    if pose_only:
+        return pose_only_out
+    return _returned_grads(outs) + ((dL_dpose,) if pose_Rt is not None else ())
 
 
 def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rotations, scale_modifier, transMat_precomp,
@@ -253,26 +190,17 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
     rasterize_gaussians returns, the blend pass as ONE grid over the tiles of all frames.  viewmatrices / projmatrices:
     [K,4,4] (or [K,16]), camposs: [K,3].  Returns (num_rendered list[K], out_color [K,3,H,W], out_others [K,7,H,W],
     radii [K,P], geomBuffers, binningBuffers, imgBuffers: lists of K uint8 tensors)."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    for name, t in (("background", background), ("means3D", means3D), ("colors", colors), ("opacity", opacity),
-                    ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
-                    ("viewmatrices", viewmatrices), ("projmatrices", projmatrices), ("sh", sh), ("camposs", camposs)):
-        _check_cuda(t, name)
-    L = _lib.lib()
-    dev = means3D.device
+    _check_forward_inputs(means3D, (
+        ("background", background), ("means3D", means3D), ("colors", colors), ("opacity", opacity), ("scales", scales),
+        ("rotations", rotations), ("transMat_precomp", transMat_precomp), ("viewmatrices", viewmatrices),
+        ("projmatrices", projmatrices), ("sh", sh), ("camposs", camposs)))
     K = viewmatrices.size(0)
     if not 1 <= K <= _lib.MAX_FRAMES or projmatrices.size(0) != K or camposs.size(0) != K:
         raise RuntimeError(f"need 1..{_lib.MAX_FRAMES} frames with one view matrix, projection matrix and camera position each")
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-    alloc = torch.zeros if P == 0 else torch.empty
-    out_color = alloc((K, NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
-    out_others = alloc((K, 7, H, W), dtype=torch.float32, device=dev)
-    radii = alloc((K, P), dtype=torch.int32, device=dev)
-    chunks = [(_Chunk(dev), _Chunk(dev), _Chunk(dev)) for _ in range(K)]
+    H, W = int(image_height), int(image_width)
+    P, dev, out_color, out_others, radii = _forward_outputs(means3D, H, W, (K,))
     counts = (C.c_int * K)()
-    rc = 0
-    try:
+    with _chunks(dev, 3 * K) as chunks:  # frame k's geometry, binning and image chunk: chunks[3k : 3k + 3]
         if P != 0:
             M = sh.size(1) if sh.size(0) != 0 else 0
             keep = [_f32c(t) for t in (background, means3D, sh, colors, opacity, scales, rotations, transMat_precomp)]
@@ -281,24 +209,18 @@ def rasterize_gaussians_batch(background, means3D, colors, opacity, scales, rota
             pm_ = _f32c(projmatrices).reshape(K, 16)
             cp_ = _f32c(camposs).reshape(K, 3)
             io = (_lib.FrameIO * K)()
-            for k, (g, b, im) in enumerate(chunks):
+            for k in range(K):
+                g, b, im = chunks[3 * k:3 * k + 3]
                 io[k].geometry_alloc, io[k].geometry_user = g.cb, g.user
                 io[k].binning_alloc, io[k].binning_user = b.cb, b.user
                 io[k].image_alloc, io[k].image_user = im.cb, im.user
                 io[k].viewmatrix, io[k].projmatrix, io[k].cam_pos = vm_[k].data_ptr(), pm_[k].data_ptr(), cp_[k].data_ptr()
                 io[k].out_color, io[k].out_others, io[k].radii = out_color[k].data_ptr(), out_others[k].data_ptr(), radii[k].data_ptr()
-            with _on_device(dev):
-                rc = L.gs2d_forward_batch(K, io, P, int(degree), M, _ptr(bg_), W, H, _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(op_),
-                                          _ptr(sc_), float(scale_modifier), _ptr(rot_), _ptr(tm_), int(bool(use_sa)),
-                                          int(bool(debug)), counts, _stream_ptr(dev))
-    finally:
-        for trio in chunks:
-            for ch in trio:
-                ch.release()
-    if rc < 0:
-        raise RuntimeError(_lib.last_error())
-    return ([int(counts[k]) for k in range(K)], out_color, out_others, radii, [c[0].tensor for c in chunks],
-            [c[1].tensor for c in chunks], [c[2].tensor for c in chunks])
+            _lib.call("gs2d_forward_batch", dev, K, io, P, int(degree), M, _ptr(bg_), W, H, _ptr(m3_), _ptr(sh_), _ptr(col_),
+                      _ptr(op_), _ptr(sc_), float(scale_modifier), _ptr(rot_), _ptr(tm_), int(bool(use_sa)), int(bool(debug)),
+                      counts)
+    return ([int(counts[k]) for k in range(K)], out_color, out_others, radii, [c.tensor for c in chunks[0::3]],
+            [c.tensor for c in chunks[1::3]], [c.tensor for c in chunks[2::3]])
 
 
 def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scales, rotations, scale_modifier, transMat_precomp,
@@ -309,28 +231,13 @@ def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scale
     what rasterize_gaussians_backward returns for that frame (per-frame gradients).
     accumulate: frame 0's tensors additionally receive the SUM over all frames (added in frame order, in one kernel).
     grad_sink: as in rasterize_gaussians_backward, for frame 0's parameter gradients."""
-    L = _lib.lib()
     dev = means3D.device
     P = means3D.size(0)
     # dL_dout_color / dL_dout_others: [K,3,H,W] / [K,7,H,W] tensors or sequences of K per-frame tensors
     K, H, W = len(dL_dout_color), dL_dout_color[0].size(1), dL_dout_color[0].size(2)
     M = sh.size(1) if sh.size(0) != 0 else 0
-    z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    outs = []
-    for k in range(K):
-        o = {"means3D": z(P, 3), "means2D": z(P, 3), "colors": z(P, NUM_CHANNELS), "normal": None if lean else z(P, 3),
-             "opacities": z(P, 1), "transMat": None if (lean and transMat_precomp.numel() == 0) else z(P, 9), "sh": z(P, M, 3),
-             "scales": z(P, 2), "rotations": z(P, 4)}
-        if k == 0 and grad_sink:
-            for name in ("means3D", "colors", "opacities", "scales", "rotations"):
-                sk = grad_sink.get(name)
-                if sk is None:
-                    continue
-                if sk.shape != o[name].shape or sk.dtype != torch.float32 or sk.device != dev or not sk.is_contiguous():
-                    raise RuntimeError(f"grad_sink[{name!r}] must be a contiguous fp32 {tuple(o[name].shape)} tensor on {dev}")
-                o[name] = sk.detach()
-        outs.append(o)
-    rc = 0
+    has_transmat = transMat_precomp.numel() != 0
+    outs = [_grad_outputs(P, M, dev, lean, has_transmat, grad_sink if k == 0 else None) for k in range(K)]
     if P != 0:
         keep = [_f32c(t) for t in (background, means3D, sh, colors, scales, rotations, transMat_precomp)]
         bg_, m3_, sh_, col_, sc_, rot_, tm_ = keep
@@ -342,24 +249,19 @@ def rasterize_gaussians_backward_batch(background, means3D, radii, colors, scale
         radii_ = radii.contiguous()
         fr = (_lib.FrameGrad * K)()
         for k in range(K):
-            f, o = fr[k], outs[k]
+            f = fr[k]
             f.viewmatrix, f.projmatrix, f.campos = vm_[k].data_ptr(), pm_[k].data_ptr(), cp_[k].data_ptr()
             f.tan_fovx, f.tan_fovy = float(tan_fovxs[k]), float(tan_fovys[k])
             f.radii = radii_[k].data_ptr()
             f.geom_buffer, f.binning_buffer, f.img_buffer = _ptr(geomBuffers[k]), _ptr(binningBuffers[k]), _ptr(imageBuffers[k])
             f.num_rendered = int(Rs[k])
             f.dL_dpix, f.dL_depths = dc_[k].data_ptr(), do_[k].data_ptr()
-            f.dL_dmean2D, f.dL_dnormal, f.dL_dopacity = o["means2D"].data_ptr(), _ptr(o["normal"]), o["opacities"].data_ptr()
-            f.dL_dcolor, f.dL_dmean3D, f.dL_dtransMat = o["colors"].data_ptr(), o["means3D"].data_ptr(), _ptr(o["transMat"])
-            f.dL_dsh, f.dL_dscale, f.dL_drot = _ptr(o["sh"]), o["scales"].data_ptr(), o["rotations"].data_ptr()
-        with _on_device(dev):
-            rc = L.gs2d_backward_batch(K, fr, int(bool(accumulate)), P, int(degree), M, _ptr(bg_), W, H, _ptr(m3_), _ptr(sh_), _ptr(col_), _ptr(sc_),
-                                       float(scale_modifier), _ptr(rot_), _ptr(tm_), int(bool(use_sa)), int(bool(debug)),
-                                       _stream_ptr(dev))
-    if rc < 0:
-        raise RuntimeError(_lib.last_error())
-    return [(o["means2D"], o["colors"], o["opacities"], o["means3D"], o["transMat"], o["sh"], o["scales"], o["rotations"])
-            for o in outs]
+            (f.dL_dmean2D, f.dL_dnormal, f.dL_dopacity, f.dL_dcolor, f.dL_dmean3D, f.dL_dtransMat, f.dL_dsh, f.dL_dscale,
+             f.dL_drot) = map(_ptr, outs[k])
+        _lib.call("gs2d_backward_batch", dev, K, fr, int(bool(accumulate)), P, int(degree), M, _ptr(bg_), W, H, _ptr(m3_),
+                  _ptr(sh_), _ptr(col_), _ptr(sc_), float(scale_modifier), _ptr(rot_), _ptr(tm_), int(bool(use_sa)),
+                  int(bool(debug)))
+    return [_returned_grads(o) for o in outs]
 
 
 def set_deterministic(on=True):
@@ -395,16 +297,11 @@ def is_launch_ahead():
 
 def mark_visible(means3D, viewmatrix, projmatrix):
     """_C.mark_visible (rasterize_points.cu:241-260)."""
-    L = _lib.lib()
     P = means3D.size(0)
     present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
     if P != 0:
         m3_, vm_, pm_ = _f32c(means3D), _f32c(viewmatrix), _f32c(projmatrix)
-        with _on_device(means3D.device):
-            rc = L.gs2d_mark_visible(P, m3_.data_ptr(), vm_.data_ptr(), pm_.data_ptr(), present.data_ptr(),
-                                     _stream_ptr(means3D.device))
-        if rc < 0:
-            raise RuntimeError(_lib.last_error())
+        _lib.call("gs2d_mark_visible", means3D.device, P, m3_.data_ptr(), vm_.data_ptr(), pm_.data_ptr(), present.data_ptr())
     return present
 
 
@@ -451,6 +348,24 @@ def _cpu_copy(args):
     return tuple(a.detach().cpu().clone() if isinstance(a, torch.Tensor) else a for a in args)
 
 
+def _with_snapshot(fn, args, kwargs, path, message):
+    """fn(*args, **kwargs) as the reference runs it under debug=True (RAST/gaus_2dgs_rasterization/__init__.py:84-91,
+    135-142): keep a host copy of the arguments, write it to `path` if the call fails."""
+    cpu_args = _cpu_copy(args)
+    try:
+        return fn(*args, **kwargs)
+    except Exception as ex:
+        torch.save(cpu_args, path)
+        print(message)
+        raise ex
+
+
+def _grad_or_zeros(g, shape, device):
+    """An upstream gradient as the kernels need it: autograd hands None for an output that did not feed the loss
+    (set_materialize_grads(False))."""
+    return g if g is not None else torch.zeros(shape, dtype=torch.float32, device=device)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """RAST/gaus_2dgs_rasterization/__init__.py:44-161."""
 
@@ -461,16 +376,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree,
                 rs.campos, rs.use_sa, rs.prefiltered, rs.debug)
-        if rs.debug:  # RAST/gaus_2dgs_rasterization/__init__.py:84-91: keep a host copy of the arguments, dump it if the call fails
-            cpu_args = _cpu_copy(args)
-            try:
-                num_rendered, color, depth, radii, geomBuffer, binningBuffer, imgBuffer = rasterize_gaussians(*args)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                raise ex
+        if rs.debug:
+            res = _with_snapshot(rasterize_gaussians, args, {}, "snapshot_fw.dump",
+                                 "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
         else:
-            num_rendered, color, depth, radii, geomBuffer, binningBuffer, imgBuffer = rasterize_gaussians(*args)
+            res = rasterize_gaussians(*args)
+        num_rendered, color, depth, radii, geomBuffer, binningBuffer, imgBuffer = res
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
@@ -487,23 +398,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         rs = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
-        if grad_out_color is None:  # only the other image fed the loss
-            grad_out_color = torch.zeros(ctx.image_shape[0], dtype=torch.float32, device=means3D.device)
-        if grad_depth is None:
-            grad_depth = torch.zeros(ctx.image_shape[1], dtype=torch.float32, device=means3D.device)
+        grad_out_color = _grad_or_zeros(grad_out_color, ctx.image_shape[0], means3D.device)  # None: only the other image fed the loss
+        grad_depth = _grad_or_zeros(grad_depth, ctx.image_shape[1], means3D.device)
         sink, chunk_rows, on_chunk = _take_sink()  # one backward per sink; a second one raises
         args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, sh, rs.sh_degree, rs.campos, geomBuffer,
                 ctx.num_rendered, binningBuffer, imgBuffer, rs.use_sa, rs.debug)
         kw = dict(grad_sink=sink, lean=True, chunk_rows=chunk_rows, on_chunk=on_chunk)
-        if rs.debug:  # RAST/gaus_2dgs_rasterization/__init__.py:135-142
-            cpu_args = _cpu_copy(args)
-            try:
-                res = rasterize_gaussians_backward(*args, **kw)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise ex
+        if rs.debug:
+            res = _with_snapshot(rasterize_gaussians_backward, args, kw, "snapshot_bw.dump",
+                                 "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
         else:
             res = rasterize_gaussians_backward(*args, **kw)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
@@ -582,9 +486,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         saved = ctx.saved_tensors
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, vms, pms, cps = saved[:10]
         geoms, bins, imgs = saved[10:10 + K], saved[10 + K:10 + 2 * K], saved[10 + 2 * K:10 + 3 * K]
-        zeros = lambda shape: torch.zeros(shape, dtype=torch.float32, device=means3D.device)
-        grad_out_color = [g if g is not None else zeros(ctx.image_shape[0]) for g in grads[:K]]
-        grad_depth = [g if g is not None else zeros(ctx.image_shape[1]) for g in grads[K:]]
+        grad_out_color = [_grad_or_zeros(g, ctx.image_shape[0], means3D.device) for g in grads[:K]]
+        grad_depth = [_grad_or_zeros(g, ctx.image_shape[1], means3D.device) for g in grads[K:]]
         sink, chunk_rows, on_chunk = _take_sink()
         if on_chunk is not None:
             raise RuntimeError("chunked (overlapped) reduction is a one-keyframe-per-rank feature; the batched backward has none")
@@ -629,6 +532,18 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+def _operator_inputs(means3D, shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """The reference's two either-or checks (RAST/gaus_2dgs_rasterization/__init__.py:198-213), then an empty tensor in
+    the place of each input that was not given.  Returns (shs, colors_precomp, scales, rotations, cov3D_precomp)."""
+    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or (
+            (scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    return tuple(torch.empty(0, dtype=torch.float32, device=means3D.device) if t is None else t
+                 for t in (shs, colors_precomp, scales, rotations, cov3D_precomp))
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()
@@ -641,25 +556,10 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        rs = self.raster_settings
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (
-                (scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        empty = lambda: torch.empty(0, dtype=torch.float32, device=means3D.device)
-        if shs is None:
-            shs = empty()
-        if colors_precomp is None:
-            colors_precomp = empty()
-        if scales is None:
-            scales = empty()
-        if rotations is None:
-            rotations = empty()
-        if cov3D_precomp is None:
-            cov3D_precomp = empty()
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _operator_inputs(means3D, shs, colors_precomp, scales, rotations,
+                                                                                 cov3D_precomp)
         return rasterize_gaussians_apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                         cov3D_precomp, rs)
+                                         cov3D_precomp, self.raster_settings)
 
 
 class GaussianRasterizerBatch(nn.Module):
@@ -675,17 +575,8 @@ class GaussianRasterizerBatch(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (
-                (scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        empty = lambda: torch.empty(0, dtype=torch.float32, device=means3D.device)
-        shs = empty() if shs is None else shs
-        colors_precomp = empty() if colors_precomp is None else colors_precomp
-        scales = empty() if scales is None else scales
-        rotations = empty() if rotations is None else rotations
-        cov3D_precomp = empty() if cov3D_precomp is None else cov3D_precomp
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _operator_inputs(means3D, shs, colors_precomp, scales, rotations,
+                                                                                 cov3D_precomp)
         K = len(self.settings_list)
         m2 = tuple(means2D) if isinstance(means2D, (list, tuple)) else (means2D,)
         out = _RasterizeGaussiansBatch.apply(means3D, shs, colors_precomp, opacities, scales, rotations,

@@ -10,7 +10,7 @@ receives the position term only (rotations are detached, render/__init__.py:36).
 """
 import torch
 
-from . import rasterizer as _r
+from . import _lib, rasterizer as _r
 
 
 def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
@@ -34,13 +34,8 @@ def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
 def pose_quaternion(pose_Rt: torch.Tensor) -> torch.Tensor:
     """matrix_to_quaternion of the rotation block of a contiguous float32 [3,4] device tensor, computed by one tiny kernel
     (gs2d_pose_quat): no host sync and a single launch instead of ~20 PyTorch ops per tracking iteration."""
-    from . import _lib
     q = torch.empty(4, dtype=torch.float32, device=pose_Rt.device)
-    with _r._on_device(pose_Rt.device):
-        rc = _lib.lib().gs2d_pose_quat(pose_Rt.data_ptr(), q.data_ptr(),
-                                       _r._stream_ptr(pose_Rt.device))
-    if rc < 0:
-        raise RuntimeError(_lib.last_error())
+    _lib.call("gs2d_pose_quat", pose_Rt.device, pose_Rt.data_ptr(), q.data_ptr())
     return q
 
 
@@ -49,14 +44,13 @@ class _RasterizeTracking(torch.autograd.Function):
     def forward(ctx, w2c, means3D, colors_precomp, opacities, scales, rotations, raster_settings):
         rs = raster_settings
         pose_Rt = w2c[:3, :4].detach().float().contiguous()
-        # q_cam is derived from pose_Rt inside the preprocess kernels (pose_quat=None): the code of gs2d_pose_quat /
+        # q_cam is derived from pose_Rt inside the preprocess kernels (pose_quat stays None): the code of gs2d_pose_quat /
         # pose_quaternion(), without its launch
-        pose_q = None
         e = torch.empty(0, dtype=torch.float32, device=means3D.device)
         num_rendered, color, allmap, radii, geom, binning, img = _r.rasterize_gaussians(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, e, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, e, rs.sh_degree, rs.campos,
-            rs.use_sa, rs.prefiltered, rs.debug, pose_Rt=pose_Rt, pose_quat=pose_q)
+            rs.use_sa, rs.prefiltered, rs.debug, pose_Rt=pose_Rt)
         ctx.rs = rs
         ctx.num_rendered = num_rendered
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, radii, geom, binning, img, pose_Rt)
@@ -69,26 +63,21 @@ class _RasterizeTracking(torch.autograd.Function):
     def backward(ctx, grad_color, grad_radii, grad_allmap):
         rs = ctx.rs
         colors_precomp, means3D, scales, rotations, radii, geom, binning, img, pose_Rt = ctx.saved_tensors
-        pose_q = None
         e = torch.empty(0, dtype=torch.float32, device=means3D.device)
-        if grad_color is None:
-            grad_color = torch.zeros(ctx.image_shape[0], dtype=torch.float32, device=means3D.device)
-        if grad_allmap is None:
-            grad_allmap = torch.zeros(ctx.image_shape[1], dtype=torch.float32, device=means3D.device)
+        # pose_quat stays None here as in the forward: the kernels derive q_cam from pose_Rt
+        args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix,
+                rs.tanfovx, rs.tanfovy, _r._grad_or_zeros(grad_color, ctx.image_shape[0], means3D.device),
+                _r._grad_or_zeros(grad_allmap, ctx.image_shape[1], means3D.device), e, rs.sh_degree, rs.campos, geom,
+                ctx.num_rendered, binning, img, rs.use_sa, rs.debug)
         if not any(ctx.needs_input_grad[1:6]):
             # the reference's tracking renderer detaches every Gaussian parameter (render/__init__.py:31-36): only the
             # pose gradient is wanted; it is accumulated straight into the first three rows of the [4,4] result, whose
             # fourth row the same call clears (GS2D_BWD_POSE_4X4): no fill kernel
             g_w2c = torch.empty((4, 4), dtype=torch.float32, device=means3D.device)
-            _r.rasterize_gaussians_backward(
-                rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix,
-                rs.tanfovx, rs.tanfovy, grad_color, grad_allmap, e, rs.sh_degree, rs.campos, geom, ctx.num_rendered, binning,
-                img, rs.use_sa, rs.debug, pose_Rt=pose_Rt, pose_quat=pose_q, pose_only_out=g_w2c)
+            _r.rasterize_gaussians_backward(*args, pose_Rt=pose_Rt, pose_only_out=g_w2c)
             return g_w2c, None, None, None, None, None, None
         (g_means2D, g_colors, g_opac, g_means3D, g_T, g_sh, g_scales, g_rot, g_pose) = _r.rasterize_gaussians_backward(
-            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix,
-            rs.tanfovx, rs.tanfovy, grad_color, grad_allmap, e, rs.sh_degree, rs.campos, geom, ctx.num_rendered, binning,
-            img, rs.use_sa, rs.debug, pose_Rt=pose_Rt, pose_quat=pose_q, lean=True)
+            *args, pose_Rt=pose_Rt, lean=True)
         g_w2c = torch.zeros((4, 4), dtype=torch.float32, device=means3D.device)
         g_w2c[:3, :4] = g_pose
         # rotations are detached in the reference's tracking / BA renderers (render/__init__.py:36,98)

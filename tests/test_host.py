@@ -229,3 +229,80 @@ def test_kept_artifacts_of_this_round_come_from_the_trees_kernels():
         if got != h:
             stale.append((os.path.basename(path), got))
     assert not stale, f"artifacts not from the tree's kernels ({h}): {stale}"
+
+
+def test_host_ptr_is_null_for_none_and_for_empty_tensors():
+    from gaus_slam_amd import _host, densify, rasterizer
+    t = torch.zeros(3)
+    assert _host.ptr(None) is None and _host.ptr(torch.empty(0)) is None and _host.ptr(torch.empty(4, 0, 3)) is None
+    assert _host.ptr(t) == t.data_ptr() != 0
+    assert densify._ptr is _host.ptr and rasterizer._ptr is _host.ptr  # one helper, not three
+
+
+class _StubLib:
+    """A library object whose one entry records its arguments and fails."""
+
+    def __init__(self):
+        self.seen = None
+
+    def entry(self, *args):
+        self.seen = args
+        return -1
+
+    def fine(self, *args):
+        self.seen = args
+        return 7
+
+
+def test_host_call_appends_the_stream_and_raises_the_right_text(monkeypatch):
+    """_host.call on a stub library: the stream is the last argument, a negative return raises `error=` when given and the
+    library's own text otherwise, and any other return is handed back.  A CPU torch.device stands in for the GPU (its index
+    is None, so on_device enters nothing); stream_ptr is stubbed because it asks the HIP runtime."""
+    from gaus_slam_amd import _host, _lib, _map_lib
+    dev = torch.device("cpu")
+    monkeypatch.setattr(_host, "stream_ptr", lambda device: ("stream of", device))
+    stub = _StubLib()
+    with pytest.raises(RuntimeError, match="^fixed text$"):
+        _host.call(stub, lambda: "text the entry left", "entry", dev, 1, None, 2.5, error="fixed text")
+    assert stub.seen == (1, None, 2.5, ("stream of", dev))
+    with pytest.raises(RuntimeError, match="^text the entry left$"):
+        _host.call(stub, lambda: "text the entry left", "entry", dev)
+    assert stub.seen == (("stream of", dev),)
+    assert _host.call(stub, None, "fine", dev, 3, error="unused") == 7 and stub.seen == (3, ("stream of", dev))
+    # both bindings are that one path
+    for binding in (_lib, _map_lib):
+        monkeypatch.setattr(binding, "_lib", stub)
+        monkeypatch.setattr(binding, "last_error", lambda: "from the library")
+        with pytest.raises(RuntimeError, match="^from the library$"):
+            binding.call("entry", dev, 4)
+        assert stub.seen == (4, ("stream of", dev))
+        assert binding.call("fine", dev) == 7
+    with pytest.raises(RuntimeError, match="^sknn_dist2 failed$"):
+        _lib.call("entry", dev, error="sknn_dist2 failed")
+
+
+def test_chunks_leave_the_callback_registry_as_they_found_it():
+    from gaus_slam_amd import _host, rasterizer
+    assert rasterizer._Chunk is _host.Chunk
+    dev = torch.device("cpu")
+    before = dict(_host.Chunk._live)
+    with _host.chunks(dev, 3) as (a, b, c):
+        assert len({a.key, b.key, c.key}) == 3 and all(_host.Chunk._live[ch.key] is ch for ch in (a, b, c))
+        assert _host._chunk_alloc(b.key, 24) == b.tensor.data_ptr() and b.tensor.numel() == 24  # what the library's callback does
+    assert _host.Chunk._live == before and b.tensor.numel() == 24  # the memory outlives the registry entry
+    with pytest.raises(ZeroDivisionError):
+        with _host.chunks(dev, 2):
+            assert len(_host.Chunk._live) == len(before) + 2
+            1 / 0
+    assert _host.Chunk._live == before
+
+
+def test_map_binding_does_not_import_the_operator_module():
+    """The dependency points from the operator modules to the bindings to _host, never back."""
+    import subprocess
+    import sys
+    code = ("import sys; import gaus_slam_amd._map_lib, gaus_slam_amd._lib, gaus_slam_amd._host; "
+            "bad = [m for m in ('rasterizer', 'tracking', 'loss', 'optim', 'knn') if 'gaus_slam_amd.' + m in sys.modules]; "
+            "print('imported:', bad); sys.exit(1 if bad else 0)")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
