@@ -5,31 +5,23 @@ formulation of the same step on the same card, 640x480 and P = 500k Gaussians, i
 The PyTorch side restates the reference's op sequence (slam/Densify.py:8-50, utils/common_utils.py:87-103,122-160,174-243,
 scene/Gaussians.py:186-226) on device tensors and ends in FusedGaussianAdam.cat + .prune, which is what a user of this package
 had before.  Both sides start from the same rendered view (allmap) and the same optimizer state, restored before every
-repetition outside the timed window; repetitions alternate between the two sides.  A repetition is timed with the host clock
-around work that ends in a device synchronise.  Launches and copies are counted in a separate, untimed pass under
-torch.profiler; host synchronisations are those torch reports (torch.cuda.set_sync_debug_mode) plus, for the native path, the
-count reads inside the library, which torch cannot see (one per *_select call).
+repetition outside the timed window.  The protocol is that of scripts/benchlib.py; host synchronisations are those torch
+reports plus, for the native path, the count reads inside the library, which torch cannot see (one per *_select call).
 
 Writes one JSON line to profiles/densify_bench.json.  Run it under a time limit, e.g.
     timeout -k 10 300 python scripts/densify_bench.py
 """
 import argparse
 import copy
-import json
-import os
-import sys
-import time
-import warnings
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
-from gaus_slam_amd import _map_lib, build, densify  # noqa: E402
-from gaus_slam_amd.optim import FusedGaussianAdam, GaussianSoA  # noqa: E402
+from gaus_slam_amd import build, densify
+from gaus_slam_amd.optim import FusedGaussianAdam, GaussianSoA
 
 DENSIFY = dict(method="splatam", sil_thres=0.5, edge_thres=0.4, use_edge_growth=False, opacity_cuil=0.005, scale_cuil=1e-4,
                scale_max=0.1)
@@ -62,8 +54,7 @@ def make_opt(P, dev, seed=0):
                   scales=torch.log(0.002 + 0.12 * torch.rand(P, 2, generator=g) ** 2), rotations=torch.randn(P, 4, generator=g),
                   colors=torch.rand(P, 3, generator=g))
     opt = FusedGaussianAdam(GaussianSoA({k: v.to(dev) for k, v in fields.items()}), dict(xyz=1e-3))
-    opt.exp_avg.copy_(torch.randn(13 * P, generator=g))
-    opt.exp_avg_sq.copy_(torch.rand(13 * P, generator=g))
+    benchlib.seeded_moments(opt, g)
     return opt
 
 
@@ -155,35 +146,10 @@ def native_add_new_gaussians(opt, fr, cfg, rcfg):
     return densify.add_new_gaussians(opt, fr["allmap"], fr["gt_color"], fr["gt_depth"], fr["K"], fr["w2c"], cfg, rcfg)
 
 
-# ---------------------------------------------------------------------------------------------------------------- measurement
-def count_device_work(fn, fresh):
-    """Kernel launches and memory copies / sets of one call, from torch.profiler (None when the profiler records no device
-    events here), and the host synchronisations torch itself reports."""
-    from torch.profiler import ProfilerActivity, profile
-    opt = fresh()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn(opt)
-        torch.cuda.synchronize()
-    kernels = copies = 0
-    for e in prof.events():
-        if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower():
-            if "memcpy" in e.name.lower() or "memset" in e.name.lower():
-                copies += 1
-            else:
-                kernels += 1
-    opt = fresh()
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn(opt)
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    syncs = sum("synchroniz" in str(x.message).lower() for x in w)
-    torch.cuda.synchronize()
-    return (kernels or None), (copies if kernels else None), syncs
+def side(times, counts, lib_reads):
+    k, c, s = counts
+    return dict(benchlib.summary(times, "ms"), kernel_launches=k, copies_and_memsets=c, host_syncs_seen_by_torch=s,
+                host_syncs=s + lib_reads)
 
 
 def main():
@@ -191,13 +157,10 @@ def main():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=500000)
-    ap.add_argument("--reps", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--edge-growth", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "densify_bench.json"))
+    benchlib.protocol_args(ap, "densify_bench.json")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("densify_bench needs a GPU: nothing is measured without one")
+    benchlib.need_gpu("densify_bench")
     build.build()
     dev = torch.device("cuda:0")
     cfg = dict(DENSIFY, use_edge_growth=a.edge_growth)
@@ -214,39 +177,17 @@ def main():
     # (a row within float32 rounding of a prune threshold may fall either way: exp / sigmoid are not correctly rounded)
     assert results["native"][0] == results["torch"][0] and abs(final["native"] - final["torch"]) <= 2, (results, final)
 
-    times = {k: [] for k in sides}
-    for r in range(a.warmup + a.reps):
-        for name, fn in sides.items():
-            opt = fresh()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn(opt)
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            if r >= a.warmup:
-                times[name].append(dt)
-            del opt
-    counts = {name: count_device_work(fn, fresh) for name, fn in sides.items()}
+    times, _ = benchlib.time_sides(sides, a.reps, a.warmup, lambda name: fresh())
+    counts = {name: benchlib.count_device_work(fn, fresh) for name, fn in sides.items()}
     lib_reads = 2 + (1 if a.edge_growth else 0)  # one count read per *_select call, inside the library
-
-    def side(name):
-        t = sorted(times[name])
-        k, c, s = counts[name]
-        return dict(ms_median=round(t[len(t) // 2], 4), ms_min=round(t[0], 4), ms_max=round(t[-1], 4), kernel_launches=k,
-                    copies_and_memsets=c, host_syncs_seen_by_torch=s,
-                    host_syncs=s + (lib_reads if name == "native" else 0))
 
     n_added, n_pruned = results["native"]
     out = dict(bench="densify", device=torch.cuda.get_device_name(0), width=a.width, height=a.height, gaussians=a.gaussians,
                edge_growth=a.edge_growth, n_added=n_added, n_pruned=n_pruned, reps=a.reps, warmup=a.warmup,
                timing="host clock around one call ending in torch.cuda.synchronize(); sides alternate; state restored outside the window",
-               native=side("native"), torch=side("torch"),
-               map_source_hash=build.map_source_hash(), map_build_info=_map_lib.build_info(), torch_version=torch.__version__)
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write(line + "\n")
+               native=side(times["native"], counts["native"], lib_reads), torch=side(times["torch"], counts["torch"], 0),
+               **benchlib.stamp())
+    benchlib.write(out, a.out)
 
 
 if __name__ == "__main__":

@@ -12,17 +12,13 @@ Run each tree in a process of its own, under a time limit, e.g.
     timeout -k 10 120 python scripts/host_parity_dump.py > head.txt && timeout -k 10 120 python scripts/host_parity_dump.py --tree ../parent > parent.txt
 """
 import argparse
-import hashlib
-import os
-import sys
 
 import numpy as np
 import torch
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ARGS = ap.parse_args()
-sys.path.insert(0, os.path.abspath(ARGS.tree))
+import benchlib
+
+benchlib.import_tree(argparse.ArgumentParser())
 
 from gaus_slam_amd import build, loss, rasterizer, render, scene_synth, tracking  # noqa: E402
 from gaus_slam_amd.knn import distCUDA2  # noqa: E402
@@ -34,12 +30,7 @@ FIELDS = ("means3D", "opacities", "scales", "rotations", "colors")
 
 def emit(case, **tensors):
     for name, t in tensors.items():
-        if t is None:
-            print(f"{case} {name} None", flush=True)
-            continue
-        t = t.detach().cpu().contiguous()
-        digest = hashlib.sha256(f"{t.dtype}{tuple(t.shape)}".encode() + t.reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()
-        print(f"{case} {name} {digest}", flush=True)
+        print(f"{case} {name} {None if t is None else benchlib.tensor_digest(t)}", flush=True)
 
 
 def leaves_of(sc, dev, requires_grad=True):

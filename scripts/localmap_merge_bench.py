@@ -7,30 +7,25 @@ The PyTorch side is what a user of this package had (slam/Backend.py:225-227 of 
 transfer_map_params -- the published pytorch3d quaternion_to_matrix and matrix_to_quaternion restated on device tensors -- then
 torch.min against the logit of 0.01, then FusedGaussianAdam.cat, which concatenates five parameters and ten moments and copies
 them into fresh flat buffers.  Both sides start from the same optimiser state, restored before every repetition outside the
-timed window; repetitions alternate between the two sides.  A repetition is timed with the host clock around work that ends
-in a device synchronise, and with time.process_time around the same window (the CPU time the host spends issuing the work).
-Launches and copies are counted in a separate, untimed pass under torch.profiler.
+timed window.  The protocol is that of scripts/benchlib.py, with time.process_time around the same window as the host clock
+(the CPU time the host spends issuing the work and waiting for it).
 
 Writes one JSON line to profiles/localmap_merge_bench.json.  Run it under a time limit, e.g.
     timeout -k 10 300 python scripts/localmap_merge_bench.py
 """
 import argparse
 import copy
-import json
 import math
-import os
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
+from benchlib import quaternion_to_matrix
 
-from gaus_slam_amd import _map_lib, build, localmap  # noqa: E402
-from gaus_slam_amd.ba_shard import BUCKET_FIELDS  # noqa: E402
-from gaus_slam_amd.mapping import RawGaussianAdam  # noqa: E402
-from gaus_slam_amd.optim import GaussianSoA  # noqa: E402
+from gaus_slam_amd import build, localmap
+from gaus_slam_amd.ba_shard import BUCKET_FIELDS
+from gaus_slam_amd.mapping import RawGaussianAdam
+from gaus_slam_amd.optim import GaussianSoA
 
 
 def make_fields(P, g):
@@ -42,23 +37,12 @@ def make_fields(P, g):
 def make_state(P, dev, seed=0):
     g = torch.Generator().manual_seed(seed)
     opt = RawGaussianAdam(GaussianSoA({k: v.to(dev) for k, v in make_fields(P, g).items()}), dict(xyz=1e-3))
-    opt.exp_avg.copy_(torch.randn(13 * P, generator=g))
-    opt.exp_avg_sq.copy_(torch.rand(13 * P, generator=g))
+    benchlib.seeded_moments(opt, g)
     opt.step_count = 7
     return opt
 
 
 # ----------------------------------------------------------------------------------------------------- the PyTorch formulation
-def quaternion_to_matrix(q):
-    """pytorch3d.transforms.quaternion_to_matrix, as published: entries scaled by 2 / |q|^2."""
-    r, i, j, k = q.unbind(-1)
-    two_s = 2.0 / (q * q).sum(-1)
-    o = torch.stack((1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
-                     two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
-                     two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j)), -1)
-    return o.reshape(q.shape[:-1] + (3, 3))
-
-
 def _sqrt_positive_part(x):
     ret = torch.zeros_like(x)
     positive = x > 0
@@ -95,35 +79,18 @@ def native_merge(opt, params, transfer, cap):
     return localmap.merge_local_map(opt, params, transfer, opacity_cap=0.01)
 
 
-# ---------------------------------------------------------------------------------------------------------------- measurement
-def count_device_work(fn, fresh):
-    """Kernel launches and memory copies / sets of one call, from torch.profiler (None when it records no device events)."""
-    from torch.profiler import ProfilerActivity, profile
-    state = fresh()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn(state)
-        torch.cuda.synchronize()
-    kernels = copies = 0
-    for e in prof.events():
-        if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower():
-            if "memcpy" in e.name.lower() or "memset" in e.name.lower():
-                copies += 1
-            else:
-                kernels += 1
-    return (kernels or None), (copies if kernels else None)
+def side(wall, cpu, counts):
+    k, m = counts
+    return dict(benchlib.summary(wall, "ms"), **benchlib.summary(cpu, "host_cpu_ms"), kernel_launches=k, copies_and_memsets=m)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--global-rows", type=int, default=500000)
     ap.add_argument("--local-rows", type=int, default=100000)
-    ap.add_argument("--reps", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "localmap_merge_bench.json"))
+    benchlib.protocol_args(ap, "localmap_merge_bench.json")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("localmap_merge_bench needs a GPU: nothing is measured without one")
+    benchlib.need_gpu("localmap_merge_bench")
     build.build()
     dev = torch.device("cuda:0")
     P, n = a.global_rows, a.local_rows
@@ -157,40 +124,17 @@ def main():
     assert d_means < 1e-5 and d_rot < 1e-4, (d_means, d_rot)
     del done, a_, b_, qa, qb
 
-    wall, cpu = {k: [] for k in sides}, {k: [] for k in sides}
-    for r in range(a.warmup + a.reps):
-        for name, fn in sides.items():
-            state = fresh()
-            torch.cuda.synchronize()
-            c0, t0 = time.process_time(), time.perf_counter()
-            fn(state)
-            torch.cuda.synchronize()
-            dt, dc = (time.perf_counter() - t0) * 1e3, (time.process_time() - c0) * 1e3
-            if r >= a.warmup:
-                wall[name].append(dt)
-                cpu[name].append(dc)
-            del state
-    counts = {name: count_device_work(fn, fresh) for name, fn in sides.items()}
-
-    def side(name):
-        t, c = sorted(wall[name]), sorted(cpu[name])
-        k, m = counts[name]
-        return dict(ms_median=round(t[len(t) // 2], 4), ms_min=round(t[0], 4), ms_max=round(t[-1], 4),
-                    host_cpu_ms_median=round(c[len(c) // 2], 4), host_cpu_ms_min=round(c[0], 4), host_cpu_ms_max=round(c[-1], 4),
-                    kernel_launches=k, copies_and_memsets=m)
+    wall, cpu = benchlib.time_sides(sides, a.reps, a.warmup, lambda name: fresh(), cpu="window")
+    counts = {name: benchlib.count_device_work(fn, fresh, syncs=False) for name, fn in sides.items()}
 
     out = dict(bench="localmap_merge", device=torch.cuda.get_device_name(0), global_rows=P, local_rows=n, reps=a.reps, warmup=a.warmup,
                timing="host clock and process_time around one call ending in torch.cuda.synchronize(); sides alternate; state "
                       "restored outside the window",
-               native_bytes_read_plus_written=4 * (78 * P + 52 * n), native=side("native"), torch=side("torch"),
-               ranges_overlap=not (max(wall["native"]) < min(wall["torch"]) or max(wall["torch"]) < min(wall["native"])),
-               max_abs_diff_means3D=d_means, max_diff_rotations_up_to_sign=d_rot, fields=list(BUCKET_FIELDS),
-               map_source_hash=build.map_source_hash(), map_build_info=_map_lib.build_info(), torch_version=torch.__version__)
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write(line + "\n")
+               native_bytes_read_plus_written=4 * (78 * P + 52 * n),
+               native=side(wall["native"], cpu["native"], counts["native"]), torch=side(wall["torch"], cpu["torch"], counts["torch"]),
+               ranges_overlap=benchlib.ranges_overlap(wall["native"], wall["torch"]),
+               max_abs_diff_means3D=d_means, max_diff_rotations_up_to_sign=d_rot, fields=list(BUCKET_FIELDS), **benchlib.stamp())
+    benchlib.write(out, a.out)
 
 
 if __name__ == "__main__":

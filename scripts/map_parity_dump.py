@@ -10,31 +10,23 @@ under a time limit, e.g.
     timeout -k 10 300 python scripts/map_parity_dump.py > head.txt && timeout -k 10 300 python scripts/map_parity_dump.py --tree ../parent > parent.txt
 """
 import argparse
-import hashlib
 import math
-import os
-import sys
 
 import torch
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ARGS = ap.parse_args()
-sys.path.insert(0, os.path.abspath(ARGS.tree))
+import benchlib
+from benchlib import DENSIFY
+
+benchlib.import_tree(argparse.ArgumentParser())
 
 from gaus_slam_amd import _map_lib, build, densify, localmap, mapping, pose  # noqa: E402
 from gaus_slam_amd.optim import FusedGaussianAdam, GaussianSoA  # noqa: E402
 
-DENSIFY = dict(densify_grad_threshold=2e-4, percent_dense=0.01, extent=2.0, opacity_cuil=0.05, scale_cuil=5e-4, scale_max=0.1)
 LRS = dict(xyz=1e-3, opacity=5e-2, scaling=5e-3, rotation=1e-3, rgb=2.5e-3)
 
 
 def emit(name, *tensors):
-    h = hashlib.sha256()
-    for t in tensors:
-        t = t.detach().cpu().contiguous()
-        h.update(f"{t.dtype}{tuple(t.shape)}".encode() + t.view(torch.uint8).numpy().tobytes())
-    print(f"{name} {h.hexdigest()}", flush=True)
+    print(f"{name} {benchlib.tensor_digest(*tensors)}", flush=True)
 
 
 def map_buffers(opt):
@@ -53,8 +45,7 @@ def make_opt(P, dev, seed, cls=FusedGaussianAdam, activated=False):
     if activated:
         f["opacities"], f["scales"] = torch.sigmoid(f["opacities"]), f["scales"].exp()
     opt = cls(GaussianSoA({k: v.to(dev) for k, v in f.items()}), LRS)
-    opt.exp_avg.copy_(torch.randn(13 * P, generator=g))
-    opt.exp_avg_sq.copy_(torch.rand(13 * P, generator=g))
+    benchlib.seeded_moments(opt, g)
     return opt, g
 
 

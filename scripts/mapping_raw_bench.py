@@ -11,27 +11,22 @@ All three use the same operator, the same fused loss (loss.mapping_loss_and_grad
                    steps): learning rates of opacities, scales and rotations are 0 there, because Adam on activated values would
                    leave their domains.  (b) - (c) is what the two extra launches cost.
 
-Every repetition starts from the same parameters and zero moments (state is rebuilt outside the timed region).  Protocol (that
-of scripts/tracking_loop_bench.py): the sides alternate, a warm-up, 15 repetitions, the host clock around a loop of `--iters`
-iterations that ends in a device synchronise; median and min..max per side; time.process_time() per iteration as well.
+Every repetition starts from the same parameters and zero moments (state is rebuilt outside the timed region).  The protocol is
+that of scripts/benchlib.py, the window being a loop of `--iters` iterations; time.process_time() is taken around the loop
+without the final synchronise (the host time spent ISSUING it) and reported per iteration.
 
 Writes one JSON line to profiles/mapping_raw_bench.json.  Run it under a time limit, e.g.
     timeout -k 10 420 python scripts/mapping_raw_bench.py
 """
 import argparse
-import json
-import os
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
-from gaus_slam_amd import _lib, _map_lib, build, loss as gl, mapping, optim, rasterizer, render as gs_render  # noqa: E402
-from gaus_slam_amd.ba_shard import BUCKET_FIELDS, GradBucket  # noqa: E402
-from gaus_slam_amd.scene_synth import make_scene  # noqa: E402
+from gaus_slam_amd import _lib, build, loss as gl, mapping, optim, rasterizer, render as gs_render
+from gaus_slam_amd.ba_shard import BUCKET_FIELDS, GradBucket
+from gaus_slam_amd.scene_synth import make_scene
 
 LRS = dict(xyz=1e-4, opacity=5e-2, scaling=1e-3, rotation=1e-3, rgb=2.5e-3)  # configs/replica/config.py
 W_COLOR, W_DEPTH, W_DIST = 0.5, 1.0, 0.1
@@ -100,28 +95,25 @@ def activated_loop(state, frame, iters):
     return loss
 
 
+def side(wall, cpu, iters):
+    return dict(benchlib.summary(wall, "iteration_ms", 1 / iters), **benchlib.summary(cpu, "process_time_ms_per_iteration", 1 / iters))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gaussians", type=int, default=500000)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mapping_raw_bench.json"))
+    benchlib.protocol_args(ap, "mapping_raw_bench.json")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("mapping_raw_bench needs a GPU: nothing is measured without one")
+    benchlib.need_gpu("mapping_raw_bench")
     build.build()
     dev = torch.device("cuda:0")
     sc = make_scene(a.gaussians, a.width, a.height, seed=0, regime="mapping")
     settings = gs_render.settings_from_camera(sc["cam"], dev, use_sa=True)
     truth = {n: sc[n].to(dev) for n in BUCKET_FIELDS}
-    with torch.no_grad():
-        obs = rasterize(settings, truth)
-        gt_color = obs["render_color"].permute(1, 2, 0).contiguous()
-        gt_depth = (obs["allmap"][0] / (obs["allmap"][1] + 1e-6)).unsqueeze(-1).contiguous()
-    frame = (settings, gt_color, gt_depth)
+    frame = (settings,) + benchlib.observed_frame(lambda: rasterize(settings, truth))
     g = torch.Generator().manual_seed(0)
     rn = lambda *s: torch.randn(*s, generator=g).to(dev)
     P = a.gaussians
@@ -135,43 +127,19 @@ def main():
     # same work on the two raw sides, or the times are not comparable: they must descend alike from the same start
     assert abs(first["native"] - first["torch"]) <= 0.1 * abs(first["torch"]), first
 
-    wall, cpu = {k: [] for k in sides}, {k: [] for k in sides}
-    for r in range(a.warmup + a.reps):
-        for name, (make, loop) in sides.items():
-            state = make(start)
-            torch.cuda.synchronize()
-            c0, t0 = time.process_time(), time.perf_counter()
-            loop(state, frame, a.iters)
-            c1 = time.process_time()                         # host time spent ISSUING the loop, before the final wait
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            if r >= a.warmup:
-                wall[name].append(dt / a.iters)
-                cpu[name].append((c1 - c0) * 1e3 / a.iters)
-
-    def side(name):
-        t, c = sorted(wall[name]), sorted(cpu[name])
-        return dict(iteration_ms_median=round(t[len(t) // 2], 4), iteration_ms_min=round(t[0], 4), iteration_ms_max=round(t[-1], 4),
-                    process_time_ms_per_iteration_median=round(c[len(c) // 2], 4),
-                    process_time_ms_per_iteration_min=round(c[0], 4), process_time_ms_per_iteration_max=round(c[-1], 4))
-
-    res = {k: side(k) for k in sides}
-    overlap = not (res["native"]["iteration_ms_max"] < res["torch"]["iteration_ms_min"]
-                   or res["torch"]["iteration_ms_max"] < res["native"]["iteration_ms_min"])
+    loops = {name: lambda state, loop=loop: loop(state, frame, a.iters) for name, (_, loop) in sides.items()}
+    wall, cpu = benchlib.time_sides(loops, a.reps, a.warmup, lambda name: sides[name][0](start), cpu="issue")
+    res = {k: side(wall[k], cpu[k], a.iters) for k in sides}
     out = dict(bench="mapping_raw", device=torch.cuda.get_device_name(0), gaussians=a.gaussians, width=a.width, height=a.height,
                iters=a.iters, reps=a.reps, warmup=a.warmup, lrs=LRS, loss_weights=[W_COLOR, W_DEPTH, W_DIST],
                last_loss_first_run=first,
                timing="host clock around one loop of `iters` iterations ending in torch.cuda.synchronize(), divided by iters; "
                       "sides alternate; process_time() around the loop without the final synchronise, per iteration",
-               native=res["native"], torch=res["torch"], activated=res["activated"], native_torch_ranges_overlap=overlap,
+               native=res["native"], torch=res["torch"], activated=res["activated"],
+               native_torch_ranges_overlap=benchlib.ranges_overlap(wall["native"], wall["torch"]),
                extra_launches_ms_median=round(res["native"]["iteration_ms_median"] - res["activated"]["iteration_ms_median"], 4),
-               source_hash=build.source_hash(), lib_source_hash=_lib.lib_source_hash(), map_source_hash=build.map_source_hash(),
-               map_build_info=_map_lib.build_info(), torch_version=torch.__version__)
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        fh.write(line + "\n")
+               lib_source_hash=_lib.lib_source_hash(), **benchlib.stamp(rasterizer=True))
+    benchlib.write(out, a.out)
 
 
 if __name__ == "__main__":

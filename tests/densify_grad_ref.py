@@ -11,6 +11,8 @@ property this file checks, not one it assumes.  It neither imports nor copies th
 """
 import torch
 
+from tests.pytorch3d_ref import quaternion_to_matrix
+
 OLD, CLONE, CHILD0, CHILD1 = 0, 1, 2, 3
 SPLIT_DIV = 1.6  # 0.8 * N with N = 2
 
@@ -65,17 +67,6 @@ def classify(opacities, scales, accum, denom, T, D, opacity_cull, scale_cull, M)
     return dict(g=g, clone=clone, split=split, src=src_f, kind=kind_f, n_cloned=n_cloned, n_split=n_split,
                 n_pruned=int(pr.sum()), P_new=int(src_f.shape[0]), child_pruned=child_pruned,
                 old_pruned=prune_mask(o, s, opacity_cull, scale_cull, M))
-
-
-def quaternion_to_matrix(q):
-    """The published formula of pytorch3d.transforms.quaternion_to_matrix on [n,4] (r, i, j, k): entries scaled by
-    2 / |q|^2, q not normalised first."""
-    r, i, j, k = torch.unbind(q, -1)
-    two_s = 2.0 / (q * q).sum(-1)
-    o = torch.stack((1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
-                     two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
-                     two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j)), -1)
-    return o.reshape(-1, 3, 3)
 
 
 def children(means3D, scales, rotations, noise, rows, dtype):

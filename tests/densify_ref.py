@@ -15,6 +15,8 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
+from tests.pytorch3d_ref import matrix_to_quaternion
+
 
 # ------------------------------------------------------------------------------------------------------------ selection (fp32)
 def rendered_depth(allmap, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2):
@@ -113,27 +115,6 @@ def viewmatrix(lookdir, up):
     vec1 = torch.cross(vec2, vec0, dim=-1)
     vec1 = vec1 / vec1.norm(dim=-1)[:, None]
     return torch.stack([vec0, vec1, vec2], dim=-1)
-
-
-def matrix_to_quaternion(m):
-    """The published algorithm of pytorch3d.transforms.matrix_to_quaternion on [N,3,3] (what build_quaternion calls,
-    common_utils.py:29-30): q_abs through _sqrt_positive_part (0 where the argument is not > 0, NaN included), four candidates,
-    the one with the largest q_abs (first on ties), real part made >= 0.  Returns (quaternion [N,4], q_abs [N,4])."""
-    m00, m01, m02 = m[:, 0, 0], m[:, 0, 1], m[:, 0, 2]
-    m10, m11, m12 = m[:, 1, 0], m[:, 1, 1], m[:, 1, 2]
-    m20, m21, m22 = m[:, 2, 0], m[:, 2, 1], m[:, 2, 2]
-    arg = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], dim=-1)
-    q_abs = torch.where(arg > 0, torch.sqrt(torch.where(arg > 0, arg, torch.ones_like(arg))), torch.zeros_like(arg))
-    cand = torch.stack([
-        torch.stack([q_abs[:, 0] ** 2, m21 - m12, m02 - m20, m10 - m01], dim=-1),
-        torch.stack([m21 - m12, q_abs[:, 1] ** 2, m10 + m01, m02 + m20], dim=-1),
-        torch.stack([m02 - m20, m10 + m01, q_abs[:, 2] ** 2, m12 + m21], dim=-1),
-        torch.stack([m10 - m01, m20 + m02, m21 + m12, q_abs[:, 3] ** 2], dim=-1),
-    ], dim=-2)
-    cand = cand / (2.0 * q_abs[:, :, None].clamp(min=0.1))
-    best = q_abs.argmax(dim=-1)
-    q = cand[torch.arange(m.shape[0]), best]
-    return torch.where(q[:, 0:1] < 0, -q, q), q_abs
 
 
 def rotations_from_normals(normals):

@@ -1,8 +1,8 @@
 """Plain-PyTorch restatement of the reference's hand-over of a local map to the global map, as the yardstick of the localmap
 tests: Backend.transfer_map_params (slam/Backend.py:158-161), the opacity clamp (:226) and what Gaussians.add_params appends.
 
-It neither imports nor copies the reference.  pytorch3d's quaternion_to_matrix is restated from its published algorithm;
-matrix_to_quaternion and the seed formulas are those of tests/densify_ref.py.  Everything takes `dtype` and works on any
+It neither imports nor copies the reference.  pytorch3d's quaternion_to_matrix and matrix_to_quaternion are those of
+tests/pytorch3d_ref.py.  Everything takes `dtype` and works on any
 device, so that the same code is the float32 formulation (on the CPU or on the GPU) and, on the same float32 inputs promoted
 exactly, its float64 evaluation.  The inputs every localmap test uses are generated here too, once per size."""
 import functools
@@ -11,23 +11,13 @@ import math
 import numpy as np
 import torch
 
-from tests.densify_ref import matrix_to_quaternion
+from tests.pytorch3d_ref import matrix_to_quaternion, quaternion_to_matrix  # noqa: F401  (ref.quaternion_to_matrix in the tests)
+from tests.util import qdiff  # noqa: F401  (ref.qdiff in the tests)
 
 F32 = np.float32
 
 
 # ------------------------------------------------------------------------------------------------------------------ formulas
-def quaternion_to_matrix(q):
-    """The published algorithm of pytorch3d.transforms.quaternion_to_matrix on [N,4] (what build_rotation calls,
-    common_utils.py:44-45): entries scaled by 2 / |q|^2, the quaternion is NOT normalised first."""
-    r, i, j, k = q.unbind(-1)
-    two_s = 2.0 / (q * q).sum(-1)
-    o = torch.stack((1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
-                     two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
-                     two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j)), -1)
-    return o.reshape(q.shape[:-1] + (3, 3))
-
-
 def transfer_map_params(xyz, rotation, transfer):
     """Backend.py:159-160 on tensors of one dtype and device.  Returns (xyz [n,3], rotation [n,4])."""
     new_xyz = (transfer[:3, :3] @ xyz.T + transfer[:3, 3:]).T                                   # :159
@@ -47,11 +37,6 @@ def rotation_by_quaternion_product(rotation, transfer):
     """The other route the contract allows: matrix_to_quaternion(R_t), then a quaternion product with q / |q|."""
     qt = matrix_to_quaternion(transfer[None, :3, :3])[0]
     return quaternion_multiply(qt.expand_as(rotation), rotation / rotation.norm(dim=-1, keepdim=True))
-
-
-def qdiff(q, q_ref):
-    """Largest component deviation per row, up to the sign of the quaternion."""
-    return torch.minimum((q - q_ref).abs().amax(-1), (q + q_ref).abs().amax(-1))
 
 
 def orthonormality_error(transfer):

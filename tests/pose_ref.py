@@ -13,18 +13,10 @@ closed_form_grad() states the step kernel's gradient chain (include/gs2d_pose.h,
 autograd without a GPU; frame_stats() states the two per-frame reductions in float64."""
 import torch
 
+from tests.pytorch3d_ref import quaternion_to_matrix
+
 LR_KEYS = ("cam_rot_lr_init", "cam_rot_lr_final", "cam_rot_lr_max_step", "cam_trans_lr_init", "cam_trans_lr_final",
            "cam_trans_lr_max_step")
-
-
-def quaternion_to_matrix(q):
-    """pytorch3d.transforms.quaternion_to_matrix as published: (r, i, j, k), entries scaled by 2 / |q|^2."""
-    r, i, j, k = torch.unbind(q, -1)
-    two_s = 2.0 / (q * q).sum(-1)
-    o = torch.stack((1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
-                     two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
-                     two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j)), -1)
-    return o.reshape(q.shape[:-1] + (3, 3))
 
 
 def schedule(step, lr_init, lr_final, max_steps):

@@ -16,64 +16,20 @@ for every frame is in DESIGN.md section 7.1; each test prints its own figures, r
 """
 import copy
 import functools
-import math
 
 import numpy as np
 import pytest
 import torch
 
 from tests import densify_ref as ref
+from tests.map_inputs import make_frame
+from tests.util import qdiff, twice_ref
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 CFG = dict(sil_thres=0.5, edge_thres=0.4, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2)
 IDENT = torch.tensor([1.0, 0.0, 0.0, 0.0])
-
-
-def _rot(axis, deg):
-    a = np.asarray(axis, np.float64)
-    a /= np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    t = math.radians(deg)
-    return np.eye(3) + math.sin(t) * K + (1 - math.cos(t)) * K @ K
-
-
-def make_frame(W, H, pose="general", seed=0, holes="mixed"):
-    """Synthetic RGB-D frame + rendered view.  gt_depth: two tilted planes, a constant-depth wall, a depth step between two
-    tilted planes, zero-depth holes (one inside, two touching the border).  allmap: A is a smooth field that dips below
-    sil_thres / edge_thres in an interior ellipse and in two small blobs on the border; D = A * surface * (1 + noise); in one
-    well-observed patch the render lies 1.5 m behind gt (the 50 x median clause)."""
-    rng = np.random.default_rng(seed)
-    v, u = np.meshgrid((np.arange(H) + 0.5) / H, (np.arange(W) + 0.5) / W, indexing="ij")
-    surf = np.where(u < 0.36, 2.0 + 0.9 * u + 0.45 * v, 3.4 - 0.8 * u + 0.7 * v)          # two tilted planes
-    surf = np.where(u >= 0.62, np.where(v < 0.5, 1.6 + 0.5 * u + 0.3 * v, 4.0 - 0.6 * u + 0.4 * v), surf)  # the step
-    wall = (abs(u - 0.47) < 0.03) & (abs(v - 0.5) < 0.05)
-    surf = np.where(wall, 2.5, surf)
-    hole = ((u - 0.66) ** 2 / 0.009 + (v - 0.5) ** 2 / 0.03 < 1) | ((abs(u - 0.45) < 0.12) & (v < 0.09)) | ((u > 0.93) & (v > 0.9))
-    if holes == "interior":  # a lattice of zero-depth blocks that stays three pixels off the border
-        yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-        hole = ((xx // 12 + yy // 12) % 5 == 0) & (xx >= 3) & (yy >= 3) & (xx < W - 3) & (yy < H - 3)
-    gt = np.where(hole, 0.0, surf)
-    A = (0.97 - 0.9 * np.exp(-((u - 0.45) ** 2 / 0.08 + (v - 0.5) ** 2 / 0.1))
-         - 0.9 * np.exp(-((u - 0.0) ** 2 + (v - 0.3) ** 2) / 0.004) - 0.9 * np.exp(-((u - 0.45) ** 2 + v ** 2) / 0.01))
-    A = np.clip(A, 0.0, 1.0)
-    behind = (abs(u - 0.85) < 0.07) & (abs(v - 0.2) < 0.1)
-    render = np.where(behind, surf + 1.5, surf) * (1 + 1e-3 * rng.standard_normal((H, W)))
-    allmap = np.zeros((7, H, W), F32)
-    allmap[1] = A.astype(F32)
-    allmap[0] = (allmap[1] * render.astype(F32)).astype(F32)
-    K = np.array([[0.9 * W, 0, 0.5 * W - 0.2], [0, 0.93 * W, 0.5 * H + 0.3], [0, 0, 1]], F32)
-    c2w = np.eye(4)
-    if pose == "general":
-        c2w[:3, :3] = _rot((0.3, -0.8, 0.5), 37.0)
-        c2w[:3, 3] = (0.4, -1.1, 0.7)
-    w2c = np.linalg.inv(c2w).astype(F32)
-    if pose == "identity":
-        w2c = np.eye(4, dtype=F32)
-    t = torch.from_numpy
-    return dict(W=W, H=H, allmap=t(allmap), gt_color=t(rng.random((H, W, 3)).astype(F32)), gt_depth=t(gt.astype(F32)), K=t(K),
-                w2c=t(w2c), wall=t(wall.reshape(-1)), pose=pose)
 
 
 def rasterized_frame():
@@ -275,16 +231,6 @@ def test_knife_edge_pixels_are_decided_as_float32_torch_decides_them(cfg_name):
 
 
 # --------------------------------------------------------------------------------------------------------------- 2. seed values
-def _twice_ref(dev_kernel, dev_ref32, magnitude, what):
-    tol = max(2.0 * float(dev_ref32.max()), 2.0 ** -22 * float(magnitude))
-    print(f"  {what}: float32 restatement {float(dev_ref32.max()):.3e}, kernel {float(dev_kernel.max()):.3e}, allowed {tol:.3e}")
-    assert float(dev_kernel.max()) <= tol, what
-
-
-def _qdiff(q, q64):
-    return torch.minimum((q - q64).abs().amax(-1), (q + q64).abs().amax(-1))
-
-
 @pytest.mark.parametrize("mode", ["splatam", "edge"])
 @pytest.mark.parametrize("name", FRAMES)
 def test_seed_values(name, mode):
@@ -306,7 +252,7 @@ def test_seed_values(name, mode):
     assert (err <= bound).all()
     # scales
     assert torch.equal(got["scales"][:, 0], got["scales"][:, 1])
-    _twice_ref((got["scales"].double() - s64["scales"]).abs(), (s32["scales"].double() - s64["scales"]).abs(),
+    twice_ref((got["scales"].double() - s64["scales"]).abs(), (s32["scales"].double() - s64["scales"]).abs(),
                s64["scales"].abs().max(), "scales")
     # rotations
     W, H = fr["W"], fr["H"]
@@ -318,15 +264,15 @@ def test_seed_values(name, mode):
     off = ~border & ~fallback
     if off.any():
         n64 = s64["normals"][off]
-        _twice_ref((ref.quat_to_normal(got["rotations"][off].double()) - n64).abs().amax(-1),
+        twice_ref((ref.quat_to_normal(got["rotations"][off].double()) - n64).abs().amax(-1),
                    (ref.quat_to_normal(s32["rotations"][off].double()) - n64).abs().amax(-1), 1.0, "surfel normal")
     top2 = torch.topk(s64["q_abs"], 2, dim=-1).values
     well = ~border & (s64["up"].norm(dim=-1) >= 1e-2) & (top2[:, 0] - top2[:, 1] > 1e-3)
     left_out = 1.0 - float(well.sum()) / n
     print(f"  full-quaternion comparison on {int(well.sum())} of {n} seeds (left out: {100 * left_out:.2f} %)")
     assert left_out <= 0.05
-    _twice_ref(_qdiff(got["rotations"][well].double(), s64["rotations"][well]),
-               _qdiff(s32["rotations"][well].double(), s64["rotations"][well]), 1.0, "quaternion")
+    twice_ref(qdiff(got["rotations"][well].double(), s64["rotations"][well]),
+               qdiff(s32["rotations"][well].double(), s64["rotations"][well]), 1.0, "quaternion")
 
 
 def test_identity_pose_wall_and_border_seeds_are_exactly_the_identity():

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from tests import densify_grad_ref as ref
+from tests.util import twice_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -208,12 +209,6 @@ def test_copied_values_are_bit_copies_and_new_moments_are_zero(P):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3. children
-def _twice_ref(dev_kernel, dev_ref32, magnitude, what):
-    tol = max(2.0 * float(dev_ref32.max()), 2.0 ** -22 * float(magnitude))
-    print(f"  {what}: float32 restatement {float(dev_ref32.max()):.3e}, kernel {float(dev_kernel.max()):.3e}, allowed {tol:.3e}")
-    assert float(dev_kernel.max()) <= tol, what
-
-
 def _check_children(P, c, after, parents, ch, fields):
     n = parents.numel()
     if n == 0:
@@ -234,9 +229,9 @@ def _check_children(P, c, after, parents, ch, fields):
     ratio = float((local[..., 2].abs() / bound).max())
     print(f"  third local component: largest share of the 16 x 2^-24 bound {ratio:.3f}")
     assert ratio <= 1.0
-    _twice_ref((got_xyz - c64["means3D"]).abs(), (c32["means3D"].double() - c64["means3D"]).abs(),
+    twice_ref((got_xyz - c64["means3D"]).abs(), (c32["means3D"].double() - c64["means3D"]).abs(),
                (x.abs() + c64["offset"].abs()).max(), "means3D")
-    _twice_ref((got_sc[:, 0].double() - c64["scales"]).abs(), (c32["scales"].double() - c64["scales"]).abs(),
+    twice_ref((got_sc[:, 0].double() - c64["scales"]).abs(), (c32["scales"].double() - c64["scales"]).abs(),
                c64["scales"].abs().max(), "log-scales")
 
 

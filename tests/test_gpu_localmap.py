@@ -33,6 +33,7 @@ import torch
 
 from tests import densify_ref
 from tests import localmap_ref as ref
+from tests.map_inputs import make_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -297,7 +298,6 @@ def test_create_map_equals_splatam_seeding_on_an_empty_view(W, H):
     from gaus_slam_amd import densify, localmap
     from gaus_slam_amd.mapping import RawGaussianAdam
     from gaus_slam_amd.optim import FusedGaussianAdam
-    from tests.test_gpu_densify import make_frame
     fr = make_frame(W, H, "general", seed=W)
     col, dep, w2c = fr["gt_color"].cuda(), fr["gt_depth"].cuda(), fr["w2c"].cuda()
     valid = densify_ref.normal_mask(fr["gt_depth"])

@@ -599,3 +599,17 @@ def loss_knife_inputs(W, H, use_weight_norm=True, seed=0, per=400, eps=1e-6, sil
     t = torch.from_numpy
     return (t(color.reshape(3, H, W)), t(allmap.reshape(7, H, W)), t(gt_color.reshape(H, W, 3)),
             t(gt_depth.reshape(H, W, 1)), edges)
+
+
+# ------------------------------------------------------------------------------------------- shared by the map-side value tests
+def twice_ref(dev_kernel, dev_ref32, magnitude, what):
+    """The tolerance rule of the map-side value tests: the kernel may deviate from the float64 reference by at most twice
+    what the float32 restatement deviates, with a floor of 2^-22 relative to `magnitude`.  Prints the figures (run with -s)."""
+    tol = max(2.0 * float(dev_ref32.max()), 2.0 ** -22 * float(magnitude))
+    print(f"  {what}: float32 restatement {float(dev_ref32.max()):.3e}, kernel {float(dev_kernel.max()):.3e}, allowed {tol:.3e}")
+    assert float(dev_kernel.max()) <= tol, what
+
+
+def qdiff(q, q_ref):
+    """Largest component deviation per row, up to the sign of the quaternion."""
+    return torch.minimum((q - q_ref).abs().amax(-1), (q + q_ref).abs().amax(-1))
