@@ -1,7 +1,8 @@
-// What the sources of libgs2d_map_hip.so share; not part of the C ABI (that is include/gs2d_map.h and include/gs2d_pose.h).
+// What the sources of libgs2d_map_hip.so share; not part of the C ABI (that is include/gs2d_map.h, include/gs2d_pose.h and include/gs2d_eval.h).
 //   host:   the thread's error text, pointer and launch checks, the workspace layout of the select / write pairs, the table
 //           of arrays a topology change moves
-//   device: pytorch3d's two quaternion conversions, the normalised depth of a rendered view, the row copy of the write kernels
+//   device: pytorch3d's two quaternion conversions, the normalised depth of a rendered view, the row copy of the write kernels,
+//           the fixed-order double sums of a wave and of a workgroup
 // Everything but the two error functions has internal linkage, so every source compiles its own copy.
 #pragma once
 #include "../csrc/gs2d_common.h"
@@ -153,6 +154,25 @@ __device__ __forceinline__ float normalised_depth(const DepthCfg& c, float D, fl
         if (d > c.far || d < c.near) d = 0.f;
     }
     return d;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- reductions
+// Sums of doubles in a fixed order: over the 64 lanes of a wave, and over the 4 waves of a 256-thread workgroup through
+// red[4] in LDS (every thread gets the sum; red may be reused by the next call).
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+__device__ __forceinline__ double block_sum(double v, double* red)
+{
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 }  // namespace

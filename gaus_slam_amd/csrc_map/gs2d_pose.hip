@@ -173,22 +173,6 @@ constexpr int STATS_MAX_BLOCKS = GS2D_POSE_STATS_WS_DOUBLES / 3;  // 512: two wo
 
 struct StatsCfg { DepthCfg dc; float alpha_track, gt_min, alpha_key; };
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* red)
-{
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ void __launch_bounds__(256)
 frame_stats_kernel(StatsCfg c, int HWi, const float* __restrict__ allmap, const float* __restrict__ gt_depth,
                    double* __restrict__ partial)

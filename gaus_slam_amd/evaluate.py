@@ -1,0 +1,152 @@
+"""Evaluation of a map on the device: the per-frame metrics of the reference's `eval_final` (utils/eval.py:254-470) and its
+trajectory error.
+
+The reference renders every frame with `Renderer_view` and computes PSNR, MS-SSIM (both images copied to the CPU for
+`pytorch_msssim.ms_ssim`, once per frame), depth RMSE, depth L1, and at the end the ATE RMSE with `evo`.  Here the four image
+metrics of a frame are eleven launches of libgs2d_map_hip.so (gs2d_eval_frame, include/gs2d_eval.h, which states every
+definition) and no host read; `evaluate_map` renders the views with the existing operator under `torch.no_grad()`, collects one
+row per frame in a device tensor and reads the host once at the end.
+
+    m = frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth)     # float64 [EVAL_OUT_DOUBLES], on the device
+    res = evaluate_map(params, frames, est_w2cs=est, gt_w2cs=gt)                  # dict: psnr, ms_ssim, depth_rmse, depth_l1, ate_rmse
+
+Not covered: LPIPS (it needs the AlexNet weights of the `lpips` package), the TSDF mesh and its metrics, and saving the
+rendered images.
+
+No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError."""
+import numpy as np
+import torch
+
+from . import _map_lib
+from ._map_lib import (EVAL_DEPTH_L1, EVAL_DEPTH_RMSE, EVAL_LEVEL, EVAL_MS_SSIM, EVAL_MS_SSIM_C, EVAL_MSE, EVAL_N_VALID,  # noqa: F401
+                       EVAL_OUT_DOUBLES, EVAL_PSNR)
+from .densify import _check_frame, _check_tensor, _require
+
+MIN_SIDE = 160  # pytorch_msssim's assertion: the smaller side must exceed (11 - 1) * 2^4
+
+
+def _check_inputs(color, allmap, gt_color, gt_depth, out, ws):
+    """Everything frame_metrics checks, before anything is launched; returns (W, H)."""
+    W, H = _check_frame(allmap, gt_color, gt_depth, device=False)
+    _check_tensor(color, "color", shape=(3, H, W))
+    _require(min(H, W) > MIN_SIDE, f"MS-SSIM needs min(H, W) > {MIN_SIDE} (five levels of an 11-tap window), got {H}x{W}")
+    dev = allmap.device
+    tensors = [(color, "color"), (allmap, "allmap"), (gt_color, "gt_color"), (gt_depth, "gt_depth")]
+    if out is not None:
+        _require(isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (EVAL_OUT_DOUBLES,)
+                 and out.is_contiguous(), f"out must be a contiguous float64 [{EVAL_OUT_DOUBLES}] tensor")
+        tensors.append((out, "out"))
+    if ws is not None:
+        _require(isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous(),
+                 "ws must be a contiguous uint8 vector")
+        tensors.append((ws, "ws"))
+    for t, name in tensors:
+        _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
+        _require(t.device == dev, f"{name} must be on {dev}")
+    return W, H
+
+
+def workspace(width, height, device):
+    """A workspace for frames of this size (gs2d_eval_ws_bytes): pass it as `ws` to reuse it from frame to frame."""
+    n = _map_lib.lib().gs2d_eval_ws_bytes(int(width), int(height))
+    _require(n > 0, f"MS-SSIM needs min(H, W) > {MIN_SIDE}, got {height}x{width}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def frame_metrics(color, allmap, gt_color, gt_depth, *, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2,
+                  clamp_color=False, out=None, ws=None):
+    """The metrics of one rendered view against its frame (gs2d_eval_frame; eval.py:401-423), without a host read.
+    color: [3,H,W] and allmap: [7,H,W], the raw operator outputs; gt_color: [H,W,3]; gt_depth: [H,W] (or [H,W,1]).
+    Returns a float64 [EVAL_OUT_DOUBLES] device tensor -- `out` when given, which may be a row of a larger tensor -- with
+      [EVAL_PSNR] [EVAL_MS_SSIM] [EVAL_DEPTH_RMSE] [EVAL_DEPTH_L1] [EVAL_N_VALID]
+      [EVAL_MSE .. +2]        the mean squared error per channel
+      [EVAL_MS_SSIM_C .. +2]  MS-SSIM per channel
+      [EVAL_LEVEL .. +14]     [5][3]: the mean of cs at levels 0-3 and of ssim at level 4, per channel, before the relu
+    Colour and ground truth are multiplied by the mask gt_depth > 0 as in eval_final; clamp_color clamps the render to [0, 1]
+    first, as eval_nvs does.  The depth is the weight-normalised, near / far-zeroed one of render/__init__.py:46-49.
+    ws: a `workspace(W, H, device)`, or None to allocate one."""
+    W, H = _check_inputs(color, allmap, gt_color, gt_depth, out, ws)
+    dev = allmap.device
+    if ws is None:
+        ws = workspace(W, H, dev)
+    _require(ws.numel() >= _map_lib.lib().gs2d_eval_ws_bytes(W, H), "ws is too small for this image size")
+    if out is None:
+        out = torch.empty(EVAL_OUT_DOUBLES, dtype=torch.float64, device=dev)
+    _map_lib.call("gs2d_eval_frame", dev, W, H, color.data_ptr(), allmap.data_ptr(), gt_color.data_ptr(), gt_depth.data_ptr(),
+                  int(bool(use_weight_norm)), float(eps), float(depth_near), float(depth_far), int(bool(clamp_color)), ws.data_ptr(),
+                  out.data_ptr())
+    return out
+
+
+def ate_rmse(est_w2cs, gt_w2cs):
+    """The ATE RMSE of eval_final (eval.py:283-297), which there is evo's PosePath3D.align(correct_scale=False) and the APE of
+    the translation part: frames whose ground-truth pose has a non-finite entry are dropped, positions are the translations of
+    the inverted matrices, the estimate is aligned rigidly (Umeyama without scale, with the determinant correction, so a
+    mirror image is not aligned), and the result is the RMSE of the residual norms.  est_w2cs, gt_w2cs: sequences of [4,4]
+    matrices or [K,4,4] arrays / tensors.  Float64 numpy on the host after one copy."""
+    def host(ms):
+        if isinstance(ms, torch.Tensor):
+            return ms.detach().to("cpu", torch.float64).numpy()
+        if len(ms) and isinstance(ms[0], torch.Tensor):
+            return torch.stack([m.detach() for m in ms]).to("cpu", torch.float64).numpy()
+        return np.asarray(ms, dtype=np.float64)
+    est, gt = host(est_w2cs), host(gt_w2cs)
+    _require(est.ndim == 3 and est.shape[1:] == (4, 4) and est.shape == gt.shape,
+             f"est_w2cs and gt_w2cs must both be [K,4,4], got {est.shape} and {gt.shape}")
+    good = np.isfinite(gt).all(axis=(1, 2))
+    est, gt = est[good], gt[good]
+    _require(len(gt) >= 1, "no frame has a finite ground-truth pose")
+    x, y = np.linalg.inv(est)[:, :3, 3], np.linalg.inv(gt)[:, :3, 3]
+    R, t = _umeyama_rigid(x, y)
+    return float(np.sqrt(np.mean(np.sum((x @ R.T + t - y) ** 2, axis=1))))
+
+
+def _umeyama_rigid(x, y):
+    """(R, t) minimising sum |R x_i + t - y_i|^2 over proper rotations (Umeyama 1991 with the scale fixed at 1)."""
+    mx, my = x.mean(0), y.mean(0)
+    cov = (y - my).T @ (x - mx) / len(x)
+    U, _, Vt = np.linalg.svd(cov)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2, 2] = -1.0
+    R = U @ S @ Vt
+    return R, my - R @ mx
+
+
+def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2,
+                 clamp_color=False):
+    """eval_final's loop over the frames.  params: the activated leaves render.render takes, a dict with means3D, opacities,
+    scales, rotations and colors (or colors_precomp, or shs).  frames: a sequence of (settings, gt_color, gt_depth), the raster
+    settings of each view (at its estimated pose) and its RGB-D frame.  Every view is rendered under torch.no_grad() with the
+    existing operator; its metrics go to row k of one [K, EVAL_OUT_DOUBLES] device tensor, which is read once at the end.
+    Returns a dict: per-frame float64 arrays `psnr`, `ms_ssim`, `depth_rmse`, `depth_l1`, their means `mean_psnr`, ...,
+    `per_frame` (the whole [K, EVAL_OUT_DOUBLES] array) and, when both pose lists are given, `ate_rmse`."""
+    from . import render as _render
+    _require(len(frames) >= 1, "frames is empty")
+    _require((est_w2cs is None) == (gt_w2cs is None), "est_w2cs and gt_w2cs go together")
+    p = dict(params)
+    colors = p.pop("colors", None)
+    if colors is not None:
+        p["colors_precomp"] = colors
+    dev = p["means3D"].device
+    _require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
+    rows = torch.empty((len(frames), EVAL_OUT_DOUBLES), dtype=torch.float64, device=dev)
+    ws = None
+    with torch.no_grad():
+        means2D = torch.zeros_like(p["means3D"])
+        for k, (settings, gt_color, gt_depth) in enumerate(frames):
+            pkg = _render.render(settings, p["means3D"], means2D, p["opacities"], shs=p.get("shs"), colors_precomp=p.get("colors_precomp"),
+                                 scales=p["scales"], rotations=p["rotations"])
+            W, H = int(pkg["allmap"].shape[2]), int(pkg["allmap"].shape[1])
+            if ws is None or ws.numel() < _map_lib.lib().gs2d_eval_ws_bytes(W, H):
+                ws = workspace(W, H, dev)
+            frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, use_weight_norm=use_weight_norm, eps=eps,
+                          depth_near=depth_near, depth_far=depth_far, clamp_color=clamp_color, out=rows[k], ws=ws)
+    host = rows.cpu().numpy()
+    res = dict(per_frame=host)
+    for name, col in (("psnr", EVAL_PSNR), ("ms_ssim", EVAL_MS_SSIM), ("depth_rmse", EVAL_DEPTH_RMSE), ("depth_l1", EVAL_DEPTH_L1)):
+        res[name] = host[:, col].copy()
+        res["mean_" + name] = float(host[:, col].mean())
+    if est_w2cs is not None:
+        res["ate_rmse"] = ate_rmse(est_w2cs, gt_w2cs)
+    return res
