@@ -1,5 +1,5 @@
-"""ctypes binding of the map growth / pruning C ABI (include/gs2d_map.h) of the pose optimiser's (include/gs2d_pose.h) and of the
-evaluation metrics' (include/gs2d_eval.h), all in libgs2d_map_hip.so.  Like _lib.py it fails loudly when the library is missing: there is no CPU fallback."""
+"""ctypes binding of the map growth / pruning C ABI (include/gs2d_map.h) of the pose optimiser's (include/gs2d_pose.h), of the
+evaluation metrics' (include/gs2d_eval.h) and of the TSDF volume's (include/gs2d_tsdf.h), all in libgs2d_map_hip.so.  Like _lib.py it fails loudly when the library is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -11,6 +11,8 @@ EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_s
            "gs2d_map_activate", "gs2d_map_raw_step", "gs2d_map_merge"]
 POSE_EXPORTS = ["gs2d_pose_init", "gs2d_pose_step", "gs2d_pose_frame_stats"]  # include/gs2d_pose.h
 EVAL_EXPORTS = ["gs2d_eval_ws_bytes", "gs2d_eval_frame"]  # include/gs2d_eval.h
+TSDF_EXPORTS = ["gs2d_tsdf_integrate", "gs2d_tsdf_extract_ws_bytes", "gs2d_tsdf_extract_count", "gs2d_tsdf_extract_write",
+                "gs2d_tsdf_tet_case"]  # include/gs2d_tsdf.h
 MAX_ARRAYS = 16  # GS2D_MAP_MAX_ARRAYS
 WS_COUNT, WS_MEDIAN = 0, 1  # GS2D_MAP_WS_COUNT, GS2D_MAP_WS_MEDIAN: uint32 word offsets into a workspace
 # GS2D_MAP_WS_DENSIFY_*: what gs2d_map_densify_select copies to its `counts` argument
@@ -21,6 +23,7 @@ POSE_Q, POSE_T, POSE_EXP_AVG, POSE_EXP_AVG_SQ, POSE_STEPS, POSE_CONVERGED_TIMES,
 POSE_STATS_WS_DOUBLES = 1536
 # GS2D_EVAL_*: offsets in doubles into the output vector of gs2d_eval_frame
 EVAL_PSNR, EVAL_MS_SSIM, EVAL_DEPTH_RMSE, EVAL_DEPTH_L1, EVAL_N_VALID, EVAL_MSE, EVAL_MS_SSIM_C, EVAL_LEVEL, EVAL_OUT_DOUBLES = 0, 1, 2, 3, 4, 5, 8, 11, 26
+TSDF_WS_VERTICES, TSDF_WS_TRIANGLES = 0, 1  # GS2D_TSDF_WS_*: uint32 word offsets into an extraction workspace
 
 
 class PoseCfg(C.Structure):
@@ -80,6 +83,16 @@ def lib():
     L.gs2d_eval_ws_bytes.argtypes = [i, i]
     L.gs2d_eval_frame.restype = i
     L.gs2d_eval_frame.argtypes = [i, i, vp, vp, vp, vp, i, f, f, f, i, vp, vp, vp]
+    L.gs2d_tsdf_integrate.restype = i
+    L.gs2d_tsdf_integrate.argtypes = [i, i, i, f, f, f, f, f, f, vp, vp, vp, vp, vp, i, i, vp, vp, i, i, f, f, f, f, f, f, f, vp, i, vp]
+    L.gs2d_tsdf_extract_ws_bytes.restype = sz
+    L.gs2d_tsdf_extract_ws_bytes.argtypes = [i, i, i]
+    L.gs2d_tsdf_extract_count.restype = i
+    L.gs2d_tsdf_extract_count.argtypes = [i, i, i, vp, vp, vp, vp]
+    L.gs2d_tsdf_extract_write.restype = i
+    L.gs2d_tsdf_extract_write.argtypes = [i, i, i, f, f, f, f, vp, vp, vp, vp, vp, i, i, vp, vp, vp, vp]
+    L.gs2d_tsdf_tet_case.restype = C.c_uint64
+    L.gs2d_tsdf_tet_case.argtypes = [i, i]
     L.gs2d_map_build_info.restype = C.c_char_p
     L.gs2d_map_last_error.restype = C.c_char_p
     _lib = L

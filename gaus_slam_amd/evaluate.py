@@ -10,8 +10,10 @@ row per frame in a device tensor and reads the host once at the end.
     m = frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth)     # float64 [EVAL_OUT_DOUBLES], on the device
     res = evaluate_map(params, frames, est_w2cs=est, gt_w2cs=gt)                  # dict: psnr, ms_ssim, depth_rmse, depth_l1, ate_rmse
 
-Not covered: LPIPS (it needs the AlexNet weights of the `lpips` package), the TSDF mesh and its metrics, and saving the
-rendered images.
+    res = evaluate_map(params, frames, tsdf=vol, mesh_intrinsics=K)                # also fuses the renders into a tsdf.TSDFVolume
+
+Not covered: LPIPS (it needs the AlexNet weights of the `lpips` package), the mesh metrics of utils/eval_mesh.py, and saving
+the rendered images.  The TSDF mesh itself is gaus_slam_amd/tsdf.py.
 
 No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError."""
 import numpy as np
@@ -114,15 +116,25 @@ def _umeyama_rigid(x, y):
 
 
 def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2,
-                 clamp_color=False):
+                 clamp_color=False, tsdf=None, mesh_interval=1, mesh_extrinsics=None, mesh_intrinsics=None):
     """eval_final's loop over the frames.  params: the activated leaves render.render takes, a dict with means3D, opacities,
     scales, rotations and colors (or colors_precomp, or shs).  frames: a sequence of (settings, gt_color, gt_depth), the raster
     settings of each view (at its estimated pose) and its RGB-D frame.  Every view is rendered under torch.no_grad() with the
     existing operator; its metrics go to row k of one [K, EVAL_OUT_DOUBLES] device tensor, which is read once at the end.
     Returns a dict: per-frame float64 arrays `psnr`, `ms_ssim`, `depth_rmse`, `depth_l1`, their means `mean_psnr`, ...,
-    `per_frame` (the whole [K, EVAL_OUT_DOUBLES] array) and, when both pose lists are given, `ate_rmse`."""
+    `per_frame` (the whole [K, EVAL_OUT_DOUBLES] array) and, when both pose lists are given, `ate_rmse`.
+    tsdf: a tsdf.TSDFVolume.  Every mesh_interval-th frame's render -- the one made for the metrics -- is then fused into it with
+    integrate_render (eval.py:378-399), one more launch per such frame and no host read, with the same depth normalisation as
+    the metrics.  mesh_intrinsics: (fx, fy, cx, cy) or a 3x3, host values (the raster settings do not carry the principal
+    point on the host).  mesh_extrinsics: one float32 [4,4] world-to-camera matrix on the device per frame; None takes the
+    frame's own view matrix.  The reference passes est_w2c @ first_w2c @ P with P the ScanNet++ axis swap: the caller composes
+    that.  With tsdf=None nothing changes: the same launches and the same bits."""
     from . import render as _render
     _require(len(frames) >= 1, "frames is empty")
+    if tsdf is not None:
+        _require(mesh_intrinsics is not None, "tsdf needs mesh_intrinsics: (fx, fy, cx, cy) or a 3x3 matrix")
+        _require(int(mesh_interval) >= 1, "mesh_interval must be >= 1")
+        _require(mesh_extrinsics is None or len(mesh_extrinsics) == len(frames), "mesh_extrinsics must have one matrix per frame")
     _require((est_w2cs is None) == (gt_w2cs is None), "est_w2cs and gt_w2cs go together")
     p = dict(params)
     colors = p.pop("colors", None)
@@ -142,6 +154,10 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
                 ws = workspace(W, H, dev)
             frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, use_weight_norm=use_weight_norm, eps=eps,
                           depth_near=depth_near, depth_far=depth_far, clamp_color=clamp_color, out=rows[k], ws=ws)
+            if tsdf is not None and k % int(mesh_interval) == 0:
+                w2c = mesh_extrinsics[k] if mesh_extrinsics is not None else settings.viewmatrix.reshape(4, 4).t().contiguous()
+                tsdf.integrate_render(pkg["render_color"], pkg["allmap"], mesh_intrinsics, w2c, use_weight_norm=use_weight_norm,
+                                      eps=eps, depth_near=depth_near, depth_far=depth_far)
     host = rows.cpu().numpy()
     res = dict(per_frame=host)
     for name, col in (("psnr", EVAL_PSNR), ("ms_ssim", EVAL_MS_SSIM), ("depth_rmse", EVAL_DEPTH_RMSE), ("depth_l1", EVAL_DEPTH_L1)):

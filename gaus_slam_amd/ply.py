@@ -3,7 +3,10 @@
     x y z nx ny nz opacity scale_0..scale_{S-1} rot_0..rot_3  then  r g b   or   f_dc_* f_rest_*
 The reference goes through the `plyfile` package (not installed here); this is a dependency-free reader/writer of the
 same byte layout (what `PlyData([PlyElement.describe(elements, 'vertex')]).write(path)` produces), so maps saved by the
-reference can be benchmarked and maps saved here load in the reference."""
+reference can be benchmarked and maps saved here load in the reference.
+
+`save_mesh` / `read_mesh`: the coloured triangle mesh of gaus_slam_amd.tsdf as the binary little-endian PLY that
+`o3d.io.write_triangle_mesh` users expect (eval.py:458-466 writes `final_mesh.ply` that way)."""
 import os
 
 import numpy as np
@@ -114,3 +117,64 @@ def load_ply(path):
     else:
         out["rgb"] = np.stack([d["r"], d["g"], d["b"]], axis=1).astype(np.float32)
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------- meshes
+_MESH_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_MESH_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+_MESH_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\n"
+                "property list uchar int vertex_indices\nend_header\n")
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def save_mesh(path, vertices, colors, triangles):
+    """A triangle mesh as a binary little-endian PLY: vertices [V,3] as float x y z, colors [V,3] in [0, 1] as uchar red green
+    blue (round(255 c) after a clamp; a NaN becomes 0), triangles [T,3] as `vertex_indices` lists of three ints.  Arrays or
+    tensors (device tensors are copied to the host)."""
+    v, c, t = _host(vertices), _host(colors), _host(triangles)
+    if v.ndim != 2 or v.shape[1] != 3 or c.shape != v.shape or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError(f"save_mesh takes vertices [V,3], colors [V,3] and triangles [T,3], got {v.shape}, {c.shape}, {t.shape}")
+    if len(t) and (int(t.min()) < 0 or int(t.max()) >= len(v)):
+        raise ValueError("a triangle refers to a vertex that does not exist")
+    vert = np.empty(len(v), _MESH_VERTEX)
+    for j, n in enumerate("xyz"):
+        vert[n] = v[:, j]
+    c8 = np.rint(np.clip(np.nan_to_num(c.astype(np.float64), nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+    for j, n in enumerate(("red", "green", "blue")):
+        vert[n] = c8[:, j]
+    face = np.empty(len(t), _MESH_FACE)
+    face["n"], face["v"] = 3, t
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write((_MESH_HEADER % (len(v), len(t))).encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+
+
+def read_mesh(path):
+    """-> (vertices [V,3] float32, colors [V,3] uint8, triangles [T,3] int32) of a file save_mesh wrote (that header exactly)."""
+    with open(path, "rb") as fh:
+        lines = []
+        while not lines or lines[-1] != "end_header":
+            line = fh.readline()
+            if not line:
+                raise ValueError("PLY header not terminated")
+            lines.append(line.decode("ascii").strip())
+        counts = [ln.split()[2] for ln in lines if ln.startswith("element ")]
+        ours = len(counts) == 2 and all(c.isdigit() for c in counts)
+        if not ours or "\n".join(lines) + "\n" != _MESH_HEADER % tuple(int(c) for c in counts):
+            raise ValueError("not a mesh PLY as save_mesh writes it")
+        nv, nf = int(counts[0]), int(counts[1])
+        vert = np.fromfile(fh, _MESH_VERTEX, nv)
+        face = np.fromfile(fh, _MESH_FACE, nf)
+    if len(vert) != nv or len(face) != nf or (nf and not (face["n"] == 3).all()):
+        raise ValueError("PLY mesh data truncated or not triangles")
+    xyz = np.stack([vert["x"], vert["y"], vert["z"]], 1).astype(np.float32)
+    rgb = np.stack([vert["red"], vert["green"], vert["blue"]], 1)
+    return xyz, rgb, face["v"].astype(np.int32).reshape(-1, 3)
