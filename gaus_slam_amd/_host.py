@@ -1,5 +1,5 @@
 """Host helpers shared by everything above the two C ABIs (include/gs2d_rasterizer.h, include/gs2d_map.h, include/gs2d_pose.h,
-include/gs2d_eval.h, include/gs2d_tsdf.h):
+include/gs2d_eval.h, include/gs2d_tsdf.h, include/gs2d_recon.h):
 device pointers, torch's current stream, the allocator callback the libraries ask for scratch memory through, and the ONE
 sequence every library call runs (`call`).  Imports torch and ctypes only, nothing from this package: _lib.py and _map_lib.py
 bind a library each and sit on top of this module, the operator modules on top of those."""

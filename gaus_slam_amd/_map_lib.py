@@ -13,6 +13,8 @@ POSE_EXPORTS = ["gs2d_pose_init", "gs2d_pose_step", "gs2d_pose_frame_stats"]  # 
 EVAL_EXPORTS = ["gs2d_eval_ws_bytes", "gs2d_eval_frame"]  # include/gs2d_eval.h
 TSDF_EXPORTS = ["gs2d_tsdf_integrate", "gs2d_tsdf_extract_ws_bytes", "gs2d_tsdf_extract_count", "gs2d_tsdf_extract_write",
                 "gs2d_tsdf_tet_case"]  # include/gs2d_tsdf.h
+RECON_EXPORTS = ["gs2d_recon_sample_ws_bytes", "gs2d_recon_sample_surface", "gs2d_recon_grid_ws_bytes", "gs2d_recon_grid_build",
+                 "gs2d_recon_nearest", "gs2d_recon_distance_stats", "gs2d_recon_pair_sums"]  # include/gs2d_recon.h
 MAX_ARRAYS = 16  # GS2D_MAP_MAX_ARRAYS
 WS_COUNT, WS_MEDIAN = 0, 1  # GS2D_MAP_WS_COUNT, GS2D_MAP_WS_MEDIAN: uint32 word offsets into a workspace
 # GS2D_MAP_WS_DENSIFY_*: what gs2d_map_densify_select copies to its `counts` argument
@@ -24,6 +26,11 @@ POSE_STATS_WS_DOUBLES = 1536
 # GS2D_EVAL_*: offsets in doubles into the output vector of gs2d_eval_frame
 EVAL_PSNR, EVAL_MS_SSIM, EVAL_DEPTH_RMSE, EVAL_DEPTH_L1, EVAL_N_VALID, EVAL_MSE, EVAL_MS_SSIM_C, EVAL_LEVEL, EVAL_OUT_DOUBLES = 0, 1, 2, 3, 4, 5, 8, 11, 26
 TSDF_WS_VERTICES, TSDF_WS_TRIANGLES = 0, 1  # GS2D_TSDF_WS_*: uint32 word offsets into an extraction workspace
+# GS2D_RECON_*: offsets in doubles into a sampling workspace and into the outputs of gs2d_recon_distance_stats / _pair_sums
+RECON_WS_TOTAL_AREA = 0
+(RECON_STATS_COUNT, RECON_STATS_SUM, RECON_STATS_SUM_SQ, RECON_STATS_MAX, RECON_STATS_BELOW_A, RECON_STATS_BELOW_B, RECON_STATS_VALUES,
+ RECON_STATS_DOUBLES) = 0, 1, 2, 3, 4, 5, 6, 1542
+RECON_PAIR_N, RECON_PAIR_P, RECON_PAIR_Q, RECON_PAIR_PQ, RECON_PAIR_D2, RECON_PAIR_VALUES, RECON_PAIR_DOUBLES = 0, 1, 4, 7, 16, 17, 4369
 
 
 class PoseCfg(C.Structure):
@@ -93,6 +100,20 @@ def lib():
     L.gs2d_tsdf_extract_write.argtypes = [i, i, i, f, f, f, f, vp, vp, vp, vp, vp, i, i, vp, vp, vp, vp]
     L.gs2d_tsdf_tet_case.restype = C.c_uint64
     L.gs2d_tsdf_tet_case.argtypes = [i, i]
+    L.gs2d_recon_sample_ws_bytes.restype = sz
+    L.gs2d_recon_sample_ws_bytes.argtypes = [i]
+    L.gs2d_recon_sample_surface.restype = i
+    L.gs2d_recon_sample_surface.argtypes = [i, vp, i, vp, i, C.c_uint32, vp, vp, vp, vp]
+    L.gs2d_recon_grid_ws_bytes.restype = sz
+    L.gs2d_recon_grid_ws_bytes.argtypes = [i]
+    L.gs2d_recon_grid_build.restype = i
+    L.gs2d_recon_grid_build.argtypes = [i, vp, vp, vp]
+    L.gs2d_recon_nearest.restype = i
+    L.gs2d_recon_nearest.argtypes = [i, vp, vp, i, vp, vp, vp, vp, vp]
+    L.gs2d_recon_distance_stats.restype = i
+    L.gs2d_recon_distance_stats.argtypes = [i, vp, f, f, vp, vp]
+    L.gs2d_recon_pair_sums.restype = i
+    L.gs2d_recon_pair_sums.argtypes = [i, vp, vp, i, vp, vp, vp, f, vp, vp]
     L.gs2d_map_build_info.restype = C.c_char_p
     L.gs2d_map_last_error.restype = C.c_char_p
     _lib = L

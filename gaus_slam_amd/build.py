@@ -1,6 +1,7 @@
 """Builds the gfx950 shared libraries with hipcc: the rasterizer library (C ABI in include/gs2d_rasterizer.h) and the map
-growth / pruning library, which also holds the camera pose optimiser, the evaluation metrics and the TSDF volume (C ABI in
-include/gs2d_map.h, include/gs2d_pose.h, include/gs2d_eval.h and include/gs2d_tsdf.h, sources in csrc_map/).
+growth / pruning library, which also holds the camera pose optimiser, the evaluation metrics, the TSDF volume and the
+reconstruction metrics (C ABI in include/gs2d_map.h, include/gs2d_pose.h, include/gs2d_eval.h, include/gs2d_tsdf.h and
+include/gs2d_recon.h, sources in csrc_map/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -25,11 +26,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectoriz
 CSRC_MAP = os.path.join(_HERE, "csrc_map")
 MAP_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_map_hip.so")
 MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip", "gs2d_pose.hip", "gs2d_map_raw.hip", "gs2d_map_merge.hip", "gs2d_eval.hip",
-               "gs2d_tsdf.hip"]
+               "gs2d_tsdf.hip", "gs2d_recon.hip"]
 MAP_HEADER = os.path.join(_HERE, "..", "include", "gs2d_map.h")
 POSE_HEADER = os.path.join(_HERE, "..", "include", "gs2d_pose.h")
 EVAL_HEADER = os.path.join(_HERE, "..", "include", "gs2d_eval.h")
 TSDF_HEADER = os.path.join(_HERE, "..", "include", "gs2d_tsdf.h")
+RECON_HEADER = os.path.join(_HERE, "..", "include", "gs2d_recon.h")
 RASTERIZER_HEADER = os.path.join(_HERE, "..", "include", "gs2d_rasterizer.h")
 
 
@@ -86,14 +88,14 @@ def _stale():
 
 def map_source_hash():
     """source_hash() of the map library: every file under csrc_map/ plus include/gs2d_map.h, include/gs2d_pose.h,
-    include/gs2d_eval.h and include/gs2d_tsdf.h (gs2d_map_build_info reports it)."""
-    return _hash(CSRC_MAP, [MAP_HEADER, POSE_HEADER, EVAL_HEADER, TSDF_HEADER])
+    include/gs2d_eval.h, include/gs2d_tsdf.h and include/gs2d_recon.h (gs2d_map_build_info reports it)."""
+    return _hash(CSRC_MAP, [MAP_HEADER, POSE_HEADER, EVAL_HEADER, TSDF_HEADER, RECON_HEADER])
 
 
 def _map_stale():
     """The map library includes ../csrc/gs2d_scan.h and gs2d_common.h: newer copies of those make it stale as well."""
     deps = [os.path.join(CSRC_MAP, f) for f in os.listdir(CSRC_MAP)] + [MAP_HEADER, POSE_HEADER, EVAL_HEADER, TSDF_HEADER,
-                                                                        os.path.join(CSRC, "gs2d_scan.h"),
+                                                                        RECON_HEADER, os.path.join(CSRC, "gs2d_scan.h"),
                                                                         os.path.join(CSRC, "gs2d_common.h")]
     return _is_stale(MAP_LIB_PATH, map_source_hash(), deps)
 
