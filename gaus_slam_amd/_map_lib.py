@@ -1,20 +1,13 @@
-"""ctypes binding of the map growth / pruning C ABI (include/gs2d_map.h) of the pose optimiser's (include/gs2d_pose.h), of the
-evaluation metrics' (include/gs2d_eval.h) and of the TSDF volume's (include/gs2d_tsdf.h), all in libgs2d_map_hip.so.  Like _lib.py it fails loudly when the library is missing: there is no CPU fallback."""
+"""ctypes binding of the five C ABIs of libgs2d_map_hip.so: map growth / pruning (include/gs2d_map.h), the pose optimiser
+(include/gs2d_pose.h), the evaluation metrics (include/gs2d_eval.h), the TSDF volume (include/gs2d_tsdf.h) and the
+reconstruction metrics (include/gs2d_recon.h).  ABI below is the one table of prototypes, grouped by header; lib() applies it
+and tests/test_abi_host.py compares it with the headers.  Like _lib.py it fails loudly when the library is missing: there is no
+CPU fallback."""
 import ctypes as C
 import os
 
 from . import _host, build as _build
 
-EXPORTS = ["gs2d_map_seed_ws_bytes", "gs2d_map_prune_ws_bytes", "gs2d_map_seed_select", "gs2d_map_seed_write",
-           "gs2d_map_prune_select", "gs2d_map_compact", "gs2d_map_densify_stats", "gs2d_map_densify_ws_bytes",
-           "gs2d_map_densify_select", "gs2d_map_densify_write", "gs2d_map_build_info", "gs2d_map_last_error",
-           "gs2d_map_activate", "gs2d_map_raw_step", "gs2d_map_merge"]
-POSE_EXPORTS = ["gs2d_pose_init", "gs2d_pose_step", "gs2d_pose_frame_stats"]  # include/gs2d_pose.h
-EVAL_EXPORTS = ["gs2d_eval_ws_bytes", "gs2d_eval_frame"]  # include/gs2d_eval.h
-TSDF_EXPORTS = ["gs2d_tsdf_integrate", "gs2d_tsdf_extract_ws_bytes", "gs2d_tsdf_extract_count", "gs2d_tsdf_extract_write",
-                "gs2d_tsdf_tet_case"]  # include/gs2d_tsdf.h
-RECON_EXPORTS = ["gs2d_recon_sample_ws_bytes", "gs2d_recon_sample_surface", "gs2d_recon_grid_ws_bytes", "gs2d_recon_grid_build",
-                 "gs2d_recon_nearest", "gs2d_recon_distance_stats", "gs2d_recon_pair_sums"]  # include/gs2d_recon.h
 MAX_ARRAYS = 16  # GS2D_MAP_MAX_ARRAYS
 WS_COUNT, WS_MEDIAN = 0, 1  # GS2D_MAP_WS_COUNT, GS2D_MAP_WS_MEDIAN: uint32 word offsets into a workspace
 # GS2D_MAP_WS_DENSIFY_*: what gs2d_map_densify_select copies to its `counts` argument
@@ -39,6 +32,55 @@ class PoseCfg(C.Structure):
                 ("beta2", C.c_double), ("eps", C.c_double), ("converged_th", C.c_double), ("frozen", C.c_int32)]
 
 
+_vp, _i, _f, _d, _sz, _pvp = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.POINTER(C.c_void_p)
+# header -> {entry point: (restype, argtypes)}, in the order of the declarations
+ABI = {
+    "gs2d_map.h": {
+        "gs2d_map_seed_ws_bytes": (_sz, [_i, _i]),
+        "gs2d_map_prune_ws_bytes": (_sz, [_i]),
+        "gs2d_map_seed_select": (_i, [_i, _i, _i, _vp, _vp, _f, _f, _i, _f, _f, _f, _vp, _vp]),
+        "gs2d_map_seed_write": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _i] + [_vp] * 8),
+        "gs2d_map_prune_select": (_i, [_i, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
+        "gs2d_map_compact": (_i, [_i, _vp, _i, _pvp, _pvp, C.POINTER(_i), _vp]),
+        "gs2d_map_densify_stats": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+        "gs2d_map_densify_ws_bytes": (_sz, [_i]),
+        "gs2d_map_densify_select": (_i, [_i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, C.POINTER(C.c_uint32), _vp]),
+        "gs2d_map_densify_write": (_i, [_i, _vp, _vp, _pvp, _pvp, _i, _pvp, _pvp, C.POINTER(_i), _vp]),
+        "gs2d_map_merge": (_i, [_i, _i, _pvp, _pvp, _pvp, _i, _pvp, _pvp, C.POINTER(_i), _vp, _f, _vp]),
+        "gs2d_map_activate": (_i, [_i] + [_vp] * 7),
+        "gs2d_map_raw_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _d, _d, _f, _i, _vp, _vp]),
+        "gs2d_map_build_info": (C.c_char_p, []),
+        "gs2d_map_last_error": (C.c_char_p, []),
+    },
+    "gs2d_pose.h": {
+        "gs2d_pose_init": (_i, [_vp] * 5),
+        "gs2d_pose_step": (_i, [_vp, _vp, _vp, _vp, PoseCfg, _vp, _vp]),
+        "gs2d_pose_frame_stats": (_i, [_i, _i, _vp, _vp, _i] + [_f] * 6 + [_vp] * 3),
+    },
+    "gs2d_eval.h": {
+        "gs2d_eval_ws_bytes": (_sz, [_i, _i]),
+        "gs2d_eval_frame": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp]),
+    },
+    "gs2d_tsdf.h": {
+        # dims, origin + three lengths, five planes, image size, colour, depth, is_allmap + depth configuration, intrinsics, w2c, rgb8
+        "gs2d_tsdf_integrate": (_i, [_i] * 3 + [_f] * 6 + [_vp] * 5 + [_i, _i, _vp, _vp] + [_i, _i, _f, _f, _f] + [_f] * 4 + [_vp, _i, _vp]),
+        "gs2d_tsdf_extract_ws_bytes": (_sz, [_i, _i, _i]),
+        "gs2d_tsdf_extract_count": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+        "gs2d_tsdf_extract_write": (_i, [_i] * 3 + [_f] * 4 + [_vp] * 5 + [_i, _i] + [_vp] * 4),
+        "gs2d_tsdf_tet_case": (C.c_uint64, [_i, _i]),
+    },
+    "gs2d_recon.h": {
+        "gs2d_recon_sample_ws_bytes": (_sz, [_i]),
+        "gs2d_recon_sample_surface": (_i, [_i, _vp, _i, _vp, _i, C.c_uint32, _vp, _vp, _vp, _vp]),
+        "gs2d_recon_grid_ws_bytes": (_sz, [_i]),
+        "gs2d_recon_grid_build": (_i, [_i, _vp, _vp, _vp]),
+        "gs2d_recon_nearest": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+        "gs2d_recon_distance_stats": (_i, [_i, _vp, _f, _f, _vp, _vp]),
+        "gs2d_recon_pair_sums": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp]),
+    },
+}
+EXPORTS, POSE_EXPORTS, EVAL_EXPORTS, TSDF_EXPORTS, RECON_EXPORTS = (list(group) for group in ABI.values())
+
 _lib = None
 
 
@@ -53,69 +95,10 @@ def lib():
             "(needs hipcc); this package has no CPU fallback.")
     import torch  # noqa: F401  (first, so that the process ends up with ONE HIP runtime: see _lib.lib)
     L = C.CDLL(path)
-    vp, i, f, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    L.gs2d_map_seed_ws_bytes.restype = sz
-    L.gs2d_map_seed_ws_bytes.argtypes = [i, i]
-    L.gs2d_map_prune_ws_bytes.restype = sz
-    L.gs2d_map_prune_ws_bytes.argtypes = [i]
-    L.gs2d_map_seed_select.restype = i
-    L.gs2d_map_seed_select.argtypes = [i, i, i, vp, vp, f, f, i, f, f, f, vp, vp]
-    L.gs2d_map_seed_write.restype = i
-    L.gs2d_map_seed_write.argtypes = [i, i, i, vp, vp, vp, f, f, f, f, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.gs2d_map_prune_select.restype = i
-    L.gs2d_map_prune_select.argtypes = [i, vp, vp, i, f, f, f, vp, vp]
-    L.gs2d_map_compact.restype = i
-    L.gs2d_map_compact.argtypes = [i, vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp]
-    L.gs2d_map_densify_stats.restype = i
-    L.gs2d_map_densify_stats.argtypes = [i, vp, vp, vp, vp, vp]
-    L.gs2d_map_densify_ws_bytes.restype = sz
-    L.gs2d_map_densify_ws_bytes.argtypes = [i]
-    L.gs2d_map_densify_select.restype = i
-    L.gs2d_map_densify_select.argtypes = [i, vp, vp, vp, vp, f, f, f, f, f, vp, C.POINTER(C.c_uint32), vp]
-    L.gs2d_map_densify_write.restype = i
-    L.gs2d_map_densify_write.argtypes = [i, vp, vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp]
-    L.gs2d_map_activate.restype = i
-    L.gs2d_map_activate.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
-    L.gs2d_map_raw_step.restype = i
-    L.gs2d_map_raw_step.argtypes = [i, vp, vp, vp, vp, vp, C.POINTER(f), C.c_double, C.c_double, f, i, vp, vp]
-    L.gs2d_map_merge.restype = i
-    L.gs2d_map_merge.argtypes = [i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), vp, f, vp]
-    L.gs2d_pose_init.restype = i
-    L.gs2d_pose_init.argtypes = [vp, vp, vp, vp, vp]
-    L.gs2d_pose_step.restype = i
-    L.gs2d_pose_step.argtypes = [vp, vp, vp, vp, PoseCfg, vp, vp]
-    L.gs2d_pose_frame_stats.restype = i
-    L.gs2d_pose_frame_stats.argtypes = [i, i, vp, vp, i, f, f, f, f, f, f, vp, vp, vp]
-    L.gs2d_eval_ws_bytes.restype = sz
-    L.gs2d_eval_ws_bytes.argtypes = [i, i]
-    L.gs2d_eval_frame.restype = i
-    L.gs2d_eval_frame.argtypes = [i, i, vp, vp, vp, vp, i, f, f, f, i, vp, vp, vp]
-    L.gs2d_tsdf_integrate.restype = i
-    L.gs2d_tsdf_integrate.argtypes = [i, i, i, f, f, f, f, f, f, vp, vp, vp, vp, vp, i, i, vp, vp, i, i, f, f, f, f, f, f, f, vp, i, vp]
-    L.gs2d_tsdf_extract_ws_bytes.restype = sz
-    L.gs2d_tsdf_extract_ws_bytes.argtypes = [i, i, i]
-    L.gs2d_tsdf_extract_count.restype = i
-    L.gs2d_tsdf_extract_count.argtypes = [i, i, i, vp, vp, vp, vp]
-    L.gs2d_tsdf_extract_write.restype = i
-    L.gs2d_tsdf_extract_write.argtypes = [i, i, i, f, f, f, f, vp, vp, vp, vp, vp, i, i, vp, vp, vp, vp]
-    L.gs2d_tsdf_tet_case.restype = C.c_uint64
-    L.gs2d_tsdf_tet_case.argtypes = [i, i]
-    L.gs2d_recon_sample_ws_bytes.restype = sz
-    L.gs2d_recon_sample_ws_bytes.argtypes = [i]
-    L.gs2d_recon_sample_surface.restype = i
-    L.gs2d_recon_sample_surface.argtypes = [i, vp, i, vp, i, C.c_uint32, vp, vp, vp, vp]
-    L.gs2d_recon_grid_ws_bytes.restype = sz
-    L.gs2d_recon_grid_ws_bytes.argtypes = [i]
-    L.gs2d_recon_grid_build.restype = i
-    L.gs2d_recon_grid_build.argtypes = [i, vp, vp, vp]
-    L.gs2d_recon_nearest.restype = i
-    L.gs2d_recon_nearest.argtypes = [i, vp, vp, i, vp, vp, vp, vp, vp]
-    L.gs2d_recon_distance_stats.restype = i
-    L.gs2d_recon_distance_stats.argtypes = [i, vp, f, f, vp, vp]
-    L.gs2d_recon_pair_sums.restype = i
-    L.gs2d_recon_pair_sums.argtypes = [i, vp, vp, i, vp, vp, vp, f, vp, vp]
-    L.gs2d_map_build_info.restype = C.c_char_p
-    L.gs2d_map_last_error.restype = C.c_char_p
+    for group in ABI.values():
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

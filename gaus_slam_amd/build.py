@@ -27,11 +27,8 @@ CSRC_MAP = os.path.join(_HERE, "csrc_map")
 MAP_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_map_hip.so")
 MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip", "gs2d_pose.hip", "gs2d_map_raw.hip", "gs2d_map_merge.hip", "gs2d_eval.hip",
                "gs2d_tsdf.hip", "gs2d_recon.hip"]
-MAP_HEADER = os.path.join(_HERE, "..", "include", "gs2d_map.h")
-POSE_HEADER = os.path.join(_HERE, "..", "include", "gs2d_pose.h")
-EVAL_HEADER = os.path.join(_HERE, "..", "include", "gs2d_eval.h")
-TSDF_HEADER = os.path.join(_HERE, "..", "include", "gs2d_tsdf.h")
-RECON_HEADER = os.path.join(_HERE, "..", "include", "gs2d_recon.h")
+# the map library's C-ABI headers, in the order map_source_hash() hashes them
+MAP_HEADERS = [os.path.join(_HERE, "..", "include", f) for f in ("gs2d_map.h", "gs2d_pose.h", "gs2d_eval.h", "gs2d_tsdf.h", "gs2d_recon.h")]
 RASTERIZER_HEADER = os.path.join(_HERE, "..", "include", "gs2d_rasterizer.h")
 
 
@@ -87,16 +84,14 @@ def _stale():
 
 
 def map_source_hash():
-    """source_hash() of the map library: every file under csrc_map/ plus include/gs2d_map.h, include/gs2d_pose.h,
-    include/gs2d_eval.h, include/gs2d_tsdf.h and include/gs2d_recon.h (gs2d_map_build_info reports it)."""
-    return _hash(CSRC_MAP, [MAP_HEADER, POSE_HEADER, EVAL_HEADER, TSDF_HEADER, RECON_HEADER])
+    """source_hash() of the map library: every file under csrc_map/ plus MAP_HEADERS (gs2d_map_build_info reports it)."""
+    return _hash(CSRC_MAP, MAP_HEADERS)
 
 
 def _map_stale():
     """The map library includes ../csrc/gs2d_scan.h and gs2d_common.h: newer copies of those make it stale as well."""
-    deps = [os.path.join(CSRC_MAP, f) for f in os.listdir(CSRC_MAP)] + [MAP_HEADER, POSE_HEADER, EVAL_HEADER, TSDF_HEADER,
-                                                                        RECON_HEADER, os.path.join(CSRC, "gs2d_scan.h"),
-                                                                        os.path.join(CSRC, "gs2d_common.h")]
+    deps = [os.path.join(CSRC_MAP, f) for f in os.listdir(CSRC_MAP)] + MAP_HEADERS + [os.path.join(CSRC, "gs2d_scan.h"),
+                                                                                      os.path.join(CSRC, "gs2d_common.h")]
     return _is_stale(MAP_LIB_PATH, map_source_hash(), deps)
 
 

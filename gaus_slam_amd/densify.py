@@ -28,7 +28,8 @@ from collections import OrderedDict, namedtuple
 import torch
 
 from . import _map_lib
-from ._host import ptr as _ptr  # noqa: F401  (pose.py, mapping.py and localmap.py take it from here)
+from ._check import check_device, check_frame, check_tensor, require
+from ._host import ptr as _ptr
 from .ba_shard import BUCKET_FIELDS, BUCKET_FLOATS
 from .optim import _views
 
@@ -38,59 +39,19 @@ MODES = {"splatam": 0, "edge": 1, "all": 2}  # GS2D_MAP_MODE_*
 SeedSelection = namedtuple("SeedSelection", "n ws mode width height")
 
 
-def _require(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
-
-
-def _check_tensor(t, name, shape=None, numel=None):
-    _require(isinstance(t, torch.Tensor), f"{name} must be a torch.Tensor")
-    _require(t.dtype == torch.float32, f"{name} must be float32, got {t.dtype}")
-    if shape is not None:
-        _require(tuple(t.shape) == tuple(shape), f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if numel is not None:
-        _require(t.numel() == numel, f"{name} must have {numel} elements, got shape {tuple(t.shape)}")
-    _require(t.is_contiguous(), f"{name} must be contiguous")
-
-
-def _check_frame(allmap, gt_color, gt_depth, device=True, no_allmap=False):
-    """Shapes, dtypes and (device=True) devices of one frame; returns (W, H).  no_allmap: allmap may be None (mode "all", which
-    never reads it); the size is then gt_depth's."""
-    if allmap is None and no_allmap:
-        _require(isinstance(gt_depth, torch.Tensor) and gt_depth.dim() in (2, 3), "gt_depth must be [H,W] or [H,W,1]")
-        H, W = int(gt_depth.shape[0]), int(gt_depth.shape[1])
-        _require(H >= 1 and W >= 1 and H * W <= 1 << 30, "gt_depth must have 1 <= H*W <= 2^30 pixels")
-    else:
-        _require(isinstance(allmap, torch.Tensor) and allmap.dim() == 3 and allmap.shape[0] == 7,
-                 "allmap must be the [7,H,W] rasterizer output")
-        H, W = int(allmap.shape[1]), int(allmap.shape[2])
-        _require(H >= 1 and W >= 1 and H * W <= 1 << 30, "allmap must have 1 <= H*W <= 2^30 pixels")
-        _check_tensor(allmap, "allmap")
-    if gt_color is not None:
-        _check_tensor(gt_color, "gt_color", shape=(H, W, 3))
-    _check_tensor(gt_depth, "gt_depth", numel=H * W)
-    _require(gt_depth.dim() >= 2 and tuple(gt_depth.shape[:2]) == (H, W), f"gt_depth must be [H,W] or [H,W,1] = [{H},{W}]")
-    dev = gt_depth.device if allmap is None else allmap.device
-    for t, name in ((allmap, "allmap"), (gt_color, "gt_color"), (gt_depth, "gt_depth")):
-        if device and t is not None:
-            _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
-            _require(t.device == dev, f"{name} must be on {dev}")
-    return W, H
-
-
 def _intrinsics(intrinsics):
     """(fx, fy, cx, cy) as Python floats from a [3,3] matrix (tensor, array or nested list).  A device tensor costs one host
     read; pass a host tensor to avoid it."""
     k = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32)
-    _require(tuple(k.shape) == (3, 3), f"intrinsics must be a [3,3] matrix, got {tuple(k.shape)}")
+    require(tuple(k.shape) == (3, 3), f"intrinsics must be a [3,3] matrix, got {tuple(k.shape)}")
     return float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
 
 
 def c2w_from_w2c(w2c):
     """The camera-to-world matrix the seeds are placed with: torch.linalg.inv(w2c) as get_pointcloud does it
     (common_utils.py:211-212), contiguous float32 [4,4] on the device of w2c."""
-    _require(isinstance(w2c, torch.Tensor) and tuple(w2c.shape) == (4, 4), "w2c must be a [4,4] tensor")
-    _require(w2c.is_cuda, "w2c must be a CUDA tensor (no CPU fallback)")
+    require(isinstance(w2c, torch.Tensor) and tuple(w2c.shape) == (4, 4), "w2c must be a [4,4] tensor")
+    check_device(None, (w2c, "w2c"))
     return torch.linalg.inv(w2c.detach().float()).contiguous()
 
 
@@ -100,11 +61,11 @@ def seed_select(allmap, gt_depth, *, mode="splatam", sil_thres=None, edge_thres=
     mode "splatam": Densify.py:16-19 (silhouette below sil_thres, or the render behind gt by more than 50 medians of the depth
     error); mode "edge": Densify.py:29-31; mode "all": every pixel (Frontend.create_map) -- allmap may then be None, and the
     thresholds and the depth configuration are not read.  Each is ANDed with the validity mask of get_pointcloud."""
-    _require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
     if mode == "all":
         sil_thres = 0.0
-    _require(sil_thres is not None, f"mode {mode!r} needs sil_thres")
-    W, H = _check_frame(allmap, None, gt_depth, no_allmap=mode == "all")
+    require(sil_thres is not None, f"mode {mode!r} needs sil_thres")
+    W, H = check_frame(allmap, None, gt_depth, no_allmap=mode == "all")
     dev = gt_depth.device
     ws = torch.empty(_map_lib.lib().gs2d_map_seed_ws_bytes(W, H), dtype=torch.uint8, device=dev)
     n = _map_lib.call("gs2d_map_seed_select", dev, MODES[mode], W, H, _ptr(allmap), gt_depth.data_ptr(), float(sil_thres),
@@ -115,7 +76,7 @@ def seed_select(allmap, gt_depth, *, mode="splatam", sil_thres=None, edge_thres=
 def seed_median(sel):
     """The lower median of the depth error that a "splatam" selection compared against, as a 0-dim float32 device tensor: word
     GS2D_MAP_WS_MEDIAN of the workspace (include/gs2d_map.h)."""
-    _require(sel.mode == "splatam", "only a splatam selection computes a median")
+    require(sel.mode == "splatam", "only a splatam selection computes a median")
     o = 4 * _map_lib.WS_MEDIAN
     return sel.ws[o:o + 4].view(torch.float32)[0]
 
@@ -123,17 +84,17 @@ def seed_median(sel):
 def seed_write(sel, allmap, gt_color, gt_depth, intrinsics, c2w, out, pixel_index=None, activated=False):
     """Writes the seeds of `sel` into `out`, a dict of BUCKET_FIELDS names to contiguous float32 [n,k] tensors (e.g. the tails
     of a re-allocated SoA); pixel_index: int32 [n] or None (gs2d_map_seed_write)."""
-    W, H = _check_frame(allmap, gt_color, gt_depth, no_allmap=sel.mode == "all")
-    _require((W, H) == (sel.width, sel.height), "the selection was computed for another image size")
+    W, H = check_frame(allmap, gt_color, gt_depth, no_allmap=sel.mode == "all")
+    require((W, H) == (sel.width, sel.height), "the selection was computed for another image size")
     dev = gt_depth.device
     for name, k in BUCKET_FIELDS.items():
-        _check_tensor(out[name], f"out[{name!r}]", shape=(sel.n, k))
-        _require(out[name].device == dev, f"out[{name!r}] must be on {dev}")
+        check_tensor(out[name], f"out[{name!r}]", shape=(sel.n, k))
+        require(out[name].device == dev, f"out[{name!r}] must be on {dev}")  # dev is the frame's: a CUDA device
     if pixel_index is not None:
-        _require(pixel_index.dtype == torch.int32 and tuple(pixel_index.shape) == (sel.n,) and pixel_index.is_contiguous()
-                 and pixel_index.device == dev, "pixel_index must be a contiguous int32 [n] tensor on the frame's device")
-    _check_tensor(c2w, "c2w", shape=(4, 4))
-    _require(c2w.device == dev, f"c2w must be on {dev}")
+        require(pixel_index.dtype == torch.int32 and tuple(pixel_index.shape) == (sel.n,) and pixel_index.is_contiguous()
+                and pixel_index.device == dev, "pixel_index must be a contiguous int32 [n] tensor on the frame's device")
+    check_tensor(c2w, "c2w", shape=(4, 4))
+    require(c2w.device == dev, f"c2w must be on {dev}")
     fx, fy, cx, cy = _intrinsics(intrinsics)
     if sel.n == 0:
         return
@@ -153,12 +114,12 @@ def seed_from_frame(allmap, gt_color, gt_depth, intrinsics, w2c, *, mode="splata
     pixel order.  The `sample_num` subsampling of get_pointcloud is not offered (see the module docstring).
     mode "all" (every valid pixel, Frontend.create_map) accepts allmap=None and needs no sil_thres.  c2w: the float32 [4,4]
     camera-to-world matrix on the device when the caller has it already; w2c is then not read."""
-    _require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
-    _require(mode == "all" or sil_thres is not None, f"mode {mode!r} needs sil_thres")
+    require(mode in MODES, f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    require(mode == "all" or sil_thres is not None, f"mode {mode!r} needs sil_thres")
     no_allmap = mode == "all"
-    _check_frame(allmap, gt_color, gt_depth, device=False, no_allmap=no_allmap)  # shapes and dtypes first, devices second
+    check_frame(allmap, gt_color, gt_depth, device=False, no_allmap=no_allmap)  # shapes and dtypes first, devices second
     _intrinsics(intrinsics)
-    _check_frame(allmap, gt_color, gt_depth, no_allmap=no_allmap)
+    check_frame(allmap, gt_color, gt_depth, no_allmap=no_allmap)
     if c2w is None:
         c2w = c2w_from_w2c(w2c)
     sel = seed_select(allmap, gt_depth, mode=mode, sil_thres=sil_thres, edge_thres=edge_thres, use_weight_norm=use_weight_norm,
@@ -173,9 +134,9 @@ def seed_from_frame(allmap, gt_color, gt_depth, intrinsics, w2c, *, mode="splata
 
 def _check_opt(opt):
     soa = opt.soa
-    _require(soa.flat.is_cuda, "the Gaussian SoA must live on a CUDA device (no CPU fallback)")
-    _require(opt.exp_avg.numel() == soa.flat.numel() and opt.exp_avg_sq.numel() == soa.flat.numel(),
-             "optimizer moments do not match the SoA")
+    require(soa.flat.is_cuda, "the Gaussian SoA must live on a CUDA device (no CPU fallback)")
+    require(opt.exp_avg.numel() == soa.flat.numel() and opt.exp_avg_sq.numel() == soa.flat.numel(),
+            "optimizer moments do not match the SoA")
 
 
 def _adopt(opt, flat, exp_avg, exp_avg_sq, P):
@@ -263,10 +224,10 @@ def add_new_gaussians(opt, allmap, gt_color, gt_depth, intrinsics, w2c, densify_
     bumped as FusedGaussianAdam.cat / prune do.  `num_addpts` is not read: the `sample_num` subsampling is not offered (every
     reference configuration sets num_addpts = h*w, which never subsamples).  Returns (n_added, n_pruned)."""
     _check_opt(opt)
-    _check_frame(allmap, gt_color, gt_depth)
-    _require(allmap.device == opt.soa.flat.device, "the frame and the Gaussian SoA must be on one device")
+    check_frame(allmap, gt_color, gt_depth)
+    require(allmap.device == opt.soa.flat.device, "the frame and the Gaussian SoA must be on one device")
     method = densify_cfg.get("method", "splatam")
-    _require(method == "splatam", f"densify method {method!r} is not supported (every reference configuration uses 'splatam')")
+    require(method == "splatam", f"densify method {method!r} is not supported (every reference configuration uses 'splatam')")
     c2w = c2w_from_w2c(w2c)
     depth = dict(use_weight_norm=render_cfg.get("use_weight_norm", True), eps=render_cfg.get("eps", 1e-6),
                  depth_near=render_cfg.get("depth_near", 1e-2), depth_far=render_cfg.get("depth_far", 1e2))
@@ -326,14 +287,13 @@ class DensificationStats:
         radii > 0: accum += |grad[:, :2]|, denom += 1 (gs2d_map_densify_stats: one launch, no host read)."""
         soa = self.opt.soa
         P = soa.P
-        _require(isinstance(radii, torch.Tensor) and radii.dtype == torch.int32, "radii must be an int32 tensor")
-        _require(tuple(radii.shape) == (P,), f"radii must have shape ({P},), got {tuple(radii.shape)}")
-        _require(radii.is_contiguous(), "radii must be contiguous")
-        _check_tensor(means2D_grad, "means2D_grad", shape=(P, 3))
+        require(isinstance(radii, torch.Tensor) and radii.dtype == torch.int32, "radii must be an int32 tensor")
+        require(tuple(radii.shape) == (P,), f"radii must have shape ({P},), got {tuple(radii.shape)}")
+        require(radii.is_contiguous(), "radii must be contiguous")
+        check_tensor(means2D_grad, "means2D_grad", shape=(P, 3))
         _check_opt(self.opt)
         dev = soa.flat.device
-        for t, name in ((radii, "radii"), (means2D_grad, "means2D_grad")):
-            _require(t.is_cuda and t.device == dev, f"{name} must be a CUDA tensor on {dev} (no CPU fallback)")
+        check_device(dev, (radii, "radii"), (means2D_grad, "means2D_grad"))
         accum, denom = self.current()
         _map_lib.call("gs2d_map_densify_stats", dev, P, radii.data_ptr(), means2D_grad.data_ptr(), accum.data_ptr(), denom.data_ptr())
 
@@ -343,12 +303,12 @@ def _densify_thresholds(cfg):
     formed in double here and rounded ONCE to float32 at the C ABI, which is what torch's comparison with a Python scalar does.
     M = 0 switches the world-size clause off (`if max_screen_size:`)."""
     for k in ("densify_grad_threshold", "percent_dense", "extent", "scale_max"):
-        _require(k in cfg, f"densify_cfg lacks {k!r}")
+        require(k in cfg, f"densify_cfg lacks {k!r}")
     cull = lambda k: cfg[k + "_cuil"] if k + "_cuil" in cfg else cfg[k + "_cull"]
     T, extent = float(cfg["densify_grad_threshold"]), float(cfg["extent"])
-    _require(C.c_float(T).value > 0, f"densify_grad_threshold must be > 0 in float32, got {T!r}: with T <= 0 the reference "
-                                     "splits the clones it has just appended, which this step does not reproduce")
-    _require(extent > 0 and extent != float("inf"), f"extent must be positive and finite, got {extent!r}")
+    require(C.c_float(T).value > 0, f"densify_grad_threshold must be > 0 in float32, got {T!r}: with T <= 0 the reference "
+                                    "splits the clones it has just appended, which this step does not reproduce")
+    require(extent > 0 and extent != float("inf"), f"extent must be positive and finite, got {extent!r}")
     return T, float(cfg["percent_dense"]) * extent, float(cull("opacity")), float(cull("scale")), (0.1 * extent if cfg["scale_max"] else 0.0)
 
 
@@ -366,7 +326,7 @@ def densify_and_prune(opt, stats, densify_cfg, generator=None):
     buffers are re-allocated even when nothing changes, `soa.generation` is bumped (stale leaves raise in
     FusedGaussianAdam.step) and `stats` is reset.  Returns DensifyResult(n_cloned, n_split, n_pruned, P_new)."""
     T, D, opacity_cull, scale_cull, M = _densify_thresholds(densify_cfg)
-    _require(isinstance(stats, DensificationStats) and stats.opt is opt, "stats must be the DensificationStats of this optimizer")
+    require(isinstance(stats, DensificationStats) and stats.opt is opt, "stats must be the DensificationStats of this optimizer")
     _check_opt(opt)
     soa = opt.soa
     P, dev = soa.P, soa.flat.device

@@ -22,36 +22,29 @@ import torch
 from . import _map_lib
 from ._map_lib import (EVAL_DEPTH_L1, EVAL_DEPTH_RMSE, EVAL_LEVEL, EVAL_MS_SSIM, EVAL_MS_SSIM_C, EVAL_MSE, EVAL_N_VALID,  # noqa: F401
                        EVAL_OUT_DOUBLES, EVAL_PSNR)
-from .densify import _check_frame, _check_tensor, _require
+from ._check import check_device, check_frame, check_tensor, check_vector, require
 
 MIN_SIDE = 160  # pytorch_msssim's assertion: the smaller side must exceed (11 - 1) * 2^4
 
 
 def _check_inputs(color, allmap, gt_color, gt_depth, out, ws):
     """Everything frame_metrics checks, before anything is launched; returns (W, H)."""
-    W, H = _check_frame(allmap, gt_color, gt_depth, device=False)
-    _check_tensor(color, "color", shape=(3, H, W))
-    _require(min(H, W) > MIN_SIDE, f"MS-SSIM needs min(H, W) > {MIN_SIDE} (five levels of an 11-tap window), got {H}x{W}")
-    dev = allmap.device
-    tensors = [(color, "color"), (allmap, "allmap"), (gt_color, "gt_color"), (gt_depth, "gt_depth")]
+    W, H = check_frame(allmap, gt_color, gt_depth, device=False)
+    check_tensor(color, "color", shape=(3, H, W))
+    require(min(H, W) > MIN_SIDE, f"MS-SSIM needs min(H, W) > {MIN_SIDE} (five levels of an 11-tap window), got {H}x{W}")
     if out is not None:
-        _require(isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (EVAL_OUT_DOUBLES,)
-                 and out.is_contiguous(), f"out must be a contiguous float64 [{EVAL_OUT_DOUBLES}] tensor")
-        tensors.append((out, "out"))
+        check_vector(out, "out", torch.float64, n=EVAL_OUT_DOUBLES, what=f"a contiguous float64 [{EVAL_OUT_DOUBLES}] tensor")
     if ws is not None:
-        _require(isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous(),
-                 "ws must be a contiguous uint8 vector")
-        tensors.append((ws, "ws"))
-    for t, name in tensors:
-        _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
-        _require(t.device == dev, f"{name} must be on {dev}")
+        check_vector(ws, "ws", torch.uint8, what="a contiguous uint8 vector")
+    check_device(allmap.device, (color, "color"), (allmap, "allmap"), (gt_color, "gt_color"), (gt_depth, "gt_depth"), (out, "out"),
+                 (ws, "ws"))
     return W, H
 
 
 def workspace(width, height, device):
     """A workspace for frames of this size (gs2d_eval_ws_bytes): pass it as `ws` to reuse it from frame to frame."""
     n = _map_lib.lib().gs2d_eval_ws_bytes(int(width), int(height))
-    _require(n > 0, f"MS-SSIM needs min(H, W) > {MIN_SIDE}, got {height}x{width}")
+    require(n > 0, f"MS-SSIM needs min(H, W) > {MIN_SIDE}, got {height}x{width}")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
@@ -71,7 +64,7 @@ def frame_metrics(color, allmap, gt_color, gt_depth, *, use_weight_norm=True, ep
     dev = allmap.device
     if ws is None:
         ws = workspace(W, H, dev)
-    _require(ws.numel() >= _map_lib.lib().gs2d_eval_ws_bytes(W, H), "ws is too small for this image size")
+    require(ws.numel() >= _map_lib.lib().gs2d_eval_ws_bytes(W, H), "ws is too small for this image size")
     if out is None:
         out = torch.empty(EVAL_OUT_DOUBLES, dtype=torch.float64, device=dev)
     _map_lib.call("gs2d_eval_frame", dev, W, H, color.data_ptr(), allmap.data_ptr(), gt_color.data_ptr(), gt_depth.data_ptr(),
@@ -93,11 +86,11 @@ def ate_rmse(est_w2cs, gt_w2cs):
             return torch.stack([m.detach() for m in ms]).to("cpu", torch.float64).numpy()
         return np.asarray(ms, dtype=np.float64)
     est, gt = host(est_w2cs), host(gt_w2cs)
-    _require(est.ndim == 3 and est.shape[1:] == (4, 4) and est.shape == gt.shape,
-             f"est_w2cs and gt_w2cs must both be [K,4,4], got {est.shape} and {gt.shape}")
+    require(est.ndim == 3 and est.shape[1:] == (4, 4) and est.shape == gt.shape,
+            f"est_w2cs and gt_w2cs must both be [K,4,4], got {est.shape} and {gt.shape}")
     good = np.isfinite(gt).all(axis=(1, 2))
     est, gt = est[good], gt[good]
-    _require(len(gt) >= 1, "no frame has a finite ground-truth pose")
+    require(len(gt) >= 1, "no frame has a finite ground-truth pose")
     x, y = np.linalg.inv(est)[:, :3, 3], np.linalg.inv(gt)[:, :3, 3]
     R, t = _umeyama_rigid(x, y)
     return float(np.sqrt(np.mean(np.sum((x @ R.T + t - y) ** 2, axis=1))))
@@ -130,18 +123,18 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     frame's own view matrix.  The reference passes est_w2c @ first_w2c @ P with P the ScanNet++ axis swap: the caller composes
     that.  With tsdf=None nothing changes: the same launches and the same bits."""
     from . import render as _render
-    _require(len(frames) >= 1, "frames is empty")
+    require(len(frames) >= 1, "frames is empty")
     if tsdf is not None:
-        _require(mesh_intrinsics is not None, "tsdf needs mesh_intrinsics: (fx, fy, cx, cy) or a 3x3 matrix")
-        _require(int(mesh_interval) >= 1, "mesh_interval must be >= 1")
-        _require(mesh_extrinsics is None or len(mesh_extrinsics) == len(frames), "mesh_extrinsics must have one matrix per frame")
-    _require((est_w2cs is None) == (gt_w2cs is None), "est_w2cs and gt_w2cs go together")
+        require(mesh_intrinsics is not None, "tsdf needs mesh_intrinsics: (fx, fy, cx, cy) or a 3x3 matrix")
+        require(int(mesh_interval) >= 1, "mesh_interval must be >= 1")
+        require(mesh_extrinsics is None or len(mesh_extrinsics) == len(frames), "mesh_extrinsics must have one matrix per frame")
+    require((est_w2cs is None) == (gt_w2cs is None), "est_w2cs and gt_w2cs go together")
     p = dict(params)
     colors = p.pop("colors", None)
     if colors is not None:
         p["colors_precomp"] = colors
     dev = p["means3D"].device
-    _require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
+    require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
     rows = torch.empty((len(frames), EVAL_OUT_DOUBLES), dtype=torch.float64, device=dev)
     ws = None
     with torch.no_grad():

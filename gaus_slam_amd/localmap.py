@@ -16,8 +16,10 @@ from collections import OrderedDict
 import torch
 
 from . import _map_lib
+from ._check import check_device, check_frame, check_tensor, require
+from ._host import ptr as _ptr
 from .ba_shard import BUCKET_FIELDS
-from .densify import _Realloc, _check_frame, _check_opt, _check_tensor, _intrinsics, _ptr, _require, seed_from_frame
+from .densify import _Realloc, _check_opt, _intrinsics, seed_from_frame
 from .mapping import RawGaussianAdam
 from .optim import FusedGaussianAdam, GaussianSoA
 
@@ -31,11 +33,11 @@ def create_map(gt_color, gt_depth, intrinsics, lrs, *, w2c=None, raw=True, betas
     learning rates of FusedGaussianAdam; w2c: [4,4] on the device, None = the identity pose, which the first frame of a local
     map has in the reference.  Returns a RawGaussianAdam on raw parameters, or with raw=False a FusedGaussianAdam on activated
     ones; moments are zero, step_count is 0.  One host read: the seed count.  A frame without a valid pixel gives 0 rows."""
-    _check_frame(None, gt_color, gt_depth, device=False, no_allmap=True)  # shapes and dtypes first, devices second
+    check_frame(None, gt_color, gt_depth, device=False, no_allmap=True)  # shapes and dtypes first, devices second
     _intrinsics(intrinsics)
     c2w = None
     if w2c is None:  # inv(I) = I: no inverse, and none of its host-side checks
-        _require(gt_depth.is_cuda, "gt_depth must be a CUDA tensor (no CPU fallback)")
+        check_device(None, (gt_depth, "gt_depth"))
         c2w = torch.eye(4, dtype=torch.float32, device=gt_depth.device)
     fields = seed_from_frame(None, gt_color, gt_depth, intrinsics, w2c, mode="all", activated=not raw, c2w=c2w)
     soa = GaussianSoA({name: fields[name] for name in BUCKET_FIELDS})
@@ -52,9 +54,8 @@ def transfer_matrix(lm_w2c, ref2f0):
     """inv(lm_w2c) @ ref2f0 (Backend.py:225): what carries a local map's parameters into the global frame.  Float32 contiguous
     [4,4] on the device of lm_w2c; no host read (the inverse is taken without torch.linalg.inv's singularity check)."""
     for t, name in ((lm_w2c, "lm_w2c"), (ref2f0, "ref2f0")):
-        _require(isinstance(t, torch.Tensor) and tuple(t.shape) == (4, 4), f"{name} must be a [4,4] tensor")
-        _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
-    _require(ref2f0.device == lm_w2c.device, f"ref2f0 must be on {lm_w2c.device}")
+        require(isinstance(t, torch.Tensor) and tuple(t.shape) == (4, 4), f"{name} must be a [4,4] tensor")
+        check_device(lm_w2c.device, (t, name))
     inv = torch.linalg.inv_ex(lm_w2c.detach().float(), check_errors=False).inverse
     return (inv @ ref2f0.detach().float()).contiguous()
 
@@ -65,7 +66,7 @@ def opacity_cap_value(opacity_cap, activated=False):
     if opacity_cap is None:
         return float("inf")
     c = torch.tensor(float(opacity_cap), dtype=torch.float32)
-    _require(bool(c > 0) and bool(c < 1), f"opacity_cap must be in (0, 1), got {opacity_cap!r}")
+    require(bool(c > 0) and bool(c < 1), f"opacity_cap must be in (0, 1), got {opacity_cap!r}")
     return float(c if activated else torch.log(c / (1 - c)))
 
 
@@ -81,21 +82,19 @@ def merge_local_map(opt, params, transfer, *, opacity_cap=0.01, activated=False)
     unchanged.  opacity_cap: c in (0,1) -- the stored logits are capped at log(c / (1 - c)), with activated=True the stored
     opacities at c; None: no cap.  Rotations are stored as the reference leaves them (raw quaternions of any length) and come
     out as unit quaternions of R_t R(q).  Returns the new row count."""
-    _require(isinstance(params, dict) and all(name in params for name in BUCKET_FIELDS),
-             f"params must be a dict with the fields {list(BUCKET_FIELDS)}")
-    _require(isinstance(params["means3D"], torch.Tensor) and params["means3D"].dim() == 2, "params['means3D'] must be [n,3]")
+    require(isinstance(params, dict) and all(name in params for name in BUCKET_FIELDS),
+            f"params must be a dict with the fields {list(BUCKET_FIELDS)}")
+    require(isinstance(params["means3D"], torch.Tensor) and params["means3D"].dim() == 2, "params['means3D'] must be [n,3]")
     n = int(params["means3D"].shape[0])
     for name, k in BUCKET_FIELDS.items():  # shapes, dtypes and strides first, devices second
-        _check_tensor(params[name], f"params[{name!r}]", shape=(n, k))
-    _check_tensor(transfer, "transfer", shape=(4, 4))
+        check_tensor(params[name], f"params[{name!r}]", shape=(n, k))
+    check_tensor(transfer, "transfer", shape=(4, 4))
     cap = opacity_cap_value(opacity_cap, activated)
     _check_opt(opt)
     soa = opt.soa
     P, dev = soa.P, soa.flat.device
-    for name in BUCKET_FIELDS:
-        _require(params[name].is_cuda and params[name].device == dev, f"params[{name!r}] must be a CUDA tensor on {dev} (no CPU fallback)")
-    _require(transfer.is_cuda and transfer.device == dev, f"transfer must be a CUDA tensor on {dev} (no CPU fallback)")
-    _require(P + n <= 1 << 29, "the merged map must have at most 2^29 rows")
+    check_device(dev, *((params[name], f"params[{name!r}]") for name in BUCKET_FIELDS), (transfer, "transfer"))
+    require(P + n <= 1 << 29, "the merged map must have at most 2^29 rows")
     r = _Realloc(opt, P + n)
     read = (transfer, *(params[name] for name in BUCKET_FIELDS)) if P + n else ()  # an empty map and nothing incoming: no launch
     if read:

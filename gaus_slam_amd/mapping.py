@@ -23,8 +23,9 @@ from collections import OrderedDict
 import torch
 
 from . import _map_lib
+from ._check import require
+from ._host import ptr as _ptr
 from .ba_shard import BUCKET_FIELDS, GradBucket
-from .densify import _ptr, _require
 from .optim import FusedGaussianAdam, _views
 
 ACT_FIELDS = OrderedDict((n, BUCKET_FIELDS[n]) for n in ("opacities", "scales", "rotations"))  # the [7P] block, in order
@@ -51,7 +52,7 @@ class RawGaussianAdam(FusedGaussianAdam):
 
     def _sync(self):
         soa = self.soa
-        _require(soa.flat.is_cuda, "RawGaussianAdam needs CUDA tensors (no CPU fallback)")
+        require(soa.flat.is_cuda, "RawGaussianAdam needs CUDA tensors (no CPU fallback)")
         if self._generation != soa.generation or self._act.numel() != ACT_FLOATS * soa.P:
             P, dev = soa.P, soa.flat.device
             self._act = torch.empty(ACT_FLOATS * P, dtype=torch.float32, device=dev)
@@ -104,19 +105,19 @@ class RawGaussianAdam(FusedGaussianAdam):
         soa = self.soa
         if leaves is not None:
             self.assert_current(leaves)
-        _require(self._act_valid, "RawGaussianAdam.step needs a render_leaves() of the present parameters first")
+        require(self._act_valid, "RawGaussianAdam.step needs a render_leaves() of the present parameters first")
         if grad_flat is None:
             grad_flat = self._bucket.flat
         for t, name in ((grad_flat, "grad_flat"), (raw_grad_out, "raw_grad_out")):
             if t is not None:
-                _require(t.numel() == soa.flat.numel() and t.dtype == torch.float32 and t.is_contiguous(),
-                         f"{name} must be a contiguous fp32 [13*P] tensor in bucket layout")
-                _require(t.device == soa.flat.device, "RawGaussianAdam needs CUDA tensors on one device (no CPU fallback)")
+                require(t.numel() == soa.flat.numel() and t.dtype == torch.float32 and t.is_contiguous(),
+                        f"{name} must be a contiguous fp32 [13*P] tensor in bucket layout")
+                require(t.device == soa.flat.device, "RawGaussianAdam needs CUDA tensors on one device (no CPU fallback)")
         if raw_grad_out is not None:  # the kernel reads and writes through __restrict__ pointers (include/gs2d_map.h)
             lo, hi = raw_grad_out.data_ptr(), raw_grad_out.data_ptr() + 4 * raw_grad_out.numel()
             for t, name in ((grad_flat, "grad_flat"), (soa.flat, "the parameters"), (self.exp_avg, "exp_avg"),
                             (self.exp_avg_sq, "exp_avg_sq"), (self._act, "the activated block")):
-                _require(hi <= t.data_ptr() or t.data_ptr() + 4 * t.numel() <= lo, f"raw_grad_out must not overlap {name}")
+                require(hi <= t.data_ptr() or t.data_ptr() + 4 * t.numel() <= lo, f"raw_grad_out must not overlap {name}")
         self.step_count += 1
         self._act_valid = False
         dev = soa.flat.device
@@ -140,15 +141,15 @@ def map_frames(opt, frames, num_iters, w_color, w_depth, w_dist, *, order=None, 
     Returns (last render package, last loss as a 0-dim device tensor, iterations run).  Nothing here reads from the device
     beyond the operator's own one read per forward (and densify_and_prune's one per call)."""
     from . import densify as _densify, loss as _loss, rasterizer as _rasterizer, render as _render
-    _require(isinstance(opt, RawGaussianAdam), "opt must be a RawGaussianAdam")
-    _require(len(frames) >= 1, "frames must hold at least one (settings, gt_color, gt_depth)")
+    require(isinstance(opt, RawGaussianAdam), "opt must be a RawGaussianAdam")
+    require(len(frames) >= 1, "frames must hold at least one (settings, gt_color, gt_depth)")
     num_iters = int(num_iters)
     if order is None:
         rng = random.Random(0)
         order = [rng.randrange(len(frames)) for _ in range(num_iters)]
-    _require(len(order) >= num_iters, "order must give a frame index for every iteration")
+    require(len(order) >= num_iters, "order must give a frame index for every iteration")
     if densify_interval:
-        _require(stats is not None and densify_cfg is not None, "densify_interval needs stats and densify_cfg")
+        require(stats is not None and densify_cfg is not None, "densify_interval needs stats and densify_cfg")
     pkg = loss = None
     done = 0
     with torch.autograd.set_multithreading_enabled(False):

@@ -17,8 +17,8 @@ No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError
 import torch
 
 from . import _map_lib
-from ._host import on_device as _on_device
-from .densify import _check_frame, _check_tensor, _ptr, _require
+from ._check import check_device, check_frame, check_tensor, require
+from ._host import on_device as _on_device, ptr as _ptr
 
 LR_KEYS = ("cam_rot_lr_init", "cam_rot_lr_final", "cam_rot_lr_max_step", "cam_trans_lr_init", "cam_trans_lr_final",
            "cam_trans_lr_max_step")
@@ -37,9 +37,9 @@ def schedule(step, lr_init, lr_final, max_steps):
 
 
 def _check_matrix(m, name, device):
-    _check_tensor(m, name, shape=(4, 4))
-    _require(m.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
-    _require(device is None or m.device == device, f"{name} must be on {device}, got {m.device}")
+    check_tensor(m, name, shape=(4, 4))
+    check_device(None, (m, name))
+    require(device is None or m.device == device, f"{name} must be on {device}, got {m.device}")
 
 
 class PoseOptimizer:
@@ -56,18 +56,18 @@ class PoseOptimizer:
     def __init__(self, initial_w2c=None, lr_dict=None, betas=(0.9, 0.99), eps=1e-8, converged_th=0.0, left=None, device=None):
         lr_dict = dict(DEFAULT_LR if lr_dict is None else lr_dict)
         for k in LR_KEYS:
-            _require(k in lr_dict, f"lr_dict lacks {k!r}")
-        _require(float(lr_dict["cam_rot_lr_max_step"]) > 0 and float(lr_dict["cam_trans_lr_max_step"]) > 0,
-                 "cam_rot_lr_max_step and cam_trans_lr_max_step must be > 0")
-        _require(0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0, f"betas must be in [0, 1), got {betas!r}")
-        _require(eps >= 0.0, f"eps must be >= 0, got {eps!r}")
+            require(k in lr_dict, f"lr_dict lacks {k!r}")
+        require(float(lr_dict["cam_rot_lr_max_step"]) > 0 and float(lr_dict["cam_trans_lr_max_step"]) > 0,
+                "cam_rot_lr_max_step and cam_trans_lr_max_step must be > 0")
+        require(0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0, f"betas must be in [0, 1), got {betas!r}")
+        require(eps >= 0.0, f"eps must be >= 0, got {eps!r}")
         for m, name in ((initial_w2c, "initial_w2c"), (left, "left")):  # before anything touches the device runtime
             if m is not None:
                 _check_matrix(m, name, None)
         if device is None:
             device = initial_w2c.device if initial_w2c is not None else (left.device if left is not None else "cuda")
         device = torch.device(device)
-        _require(device.type == "cuda", f"the pose lives on a CUDA device (no CPU fallback), got {device}")
+        require(device.type == "cuda", f"the pose lives on a CUDA device (no CPU fallback), got {device}")
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         for m, name in ((initial_w2c, "initial_w2c"), (left, "left")):
@@ -105,7 +105,7 @@ class PoseOptimizer:
         dev = self.device
         if grad is None:
             grad = self.w2c.grad
-            _require(grad is not None, "PoseOptimizer.step: .w2c has no gradient (render with it and call backward first)")
+            require(grad is not None, "PoseOptimizer.step: .w2c has no gradient (render with it and call backward first)")
         _check_matrix(grad, "grad", dev)
         left = self.left if left is None else left
         for m, name in ((left, "left"), (next_left, "next_left")):
@@ -119,8 +119,8 @@ class PoseOptimizer:
         """Restarts from a raw quaternion (w, x, y, z) -- it need not be normalised -- and a translation: float32 [4] and [3]
         tensors.  Moments and counters are zeroed and `.w2c` is rewritten.  For resuming a saved pose; not on the hot path."""
         for v, name, n in ((q, "q", 4), (t, "t", 3)):
-            _require(isinstance(v, torch.Tensor) and v.dtype == torch.float32 and tuple(v.shape) == (n,),
-                     f"{name} must be a float32 [{n}] tensor")
+            require(isinstance(v, torch.Tensor) and v.dtype == torch.float32 and tuple(v.shape) == (n,),
+                    f"{name} must be a float32 [{n}] tensor")
         with torch.no_grad():
             self._state.zero_()
             f = self._state.view(torch.float32)
@@ -184,8 +184,8 @@ def track(settings, opt, means3D, opacities, colors, scales, rotations, gt_color
     Departure from the reference: when the loop overruns the latch, the returned package was rendered AT the final pose; the
     reference's last package is rendered before its last step."""
     from . import loss as _loss, tracking
-    _require(isinstance(opt, PoseOptimizer), "opt must be a PoseOptimizer")
-    _require(num_iters >= 1, "num_iters must be >= 1")
+    require(isinstance(opt, PoseOptimizer), "opt must be a PoseOptimizer")
+    require(num_iters >= 1, "num_iters must be >= 1")
     pkg = loss = None
     with torch.autograd.set_multithreading_enabled(False):
         for it in range(num_iters):
@@ -210,7 +210,7 @@ def frame_stats(allmap, gt_depth, *, use_weight_norm=True, eps=1e-6, depth_near=
       [1] the number of pixels in that mask                            }
       [2] the number of pixels with alpha < alpha_key                    Frontend.py:186-188: keyframe when [2] > numel * tau_k
     with d the weight-normalised, near / far-zeroed depth of render/__init__.py:46-49."""
-    W, H = _check_frame(allmap, None, gt_depth)
+    W, H = check_frame(allmap, None, gt_depth)
     dev = allmap.device
     ws = torch.empty(_map_lib.POSE_STATS_WS_DOUBLES, dtype=torch.float64, device=dev)
     out = torch.empty(3, dtype=torch.float64, device=dev)

@@ -20,37 +20,33 @@ import numpy as np
 import torch
 
 from . import _map_lib
-from .densify import _check_tensor, _require
+from ._check import check_device, check_tensor, check_vector, require
 
 MAX_TARGETS = 1 << 27
 MAX_SAMPLES = 1 << 28
 
 
-def _check_cloud(t, name, most=None):
-    _require(isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == 3 and t.shape[0] >= 1, f"{name} must be [N,3] with N >= 1")
-    _check_tensor(t, name)
-    _require(most is None or t.shape[0] <= most, f"{name} must have at most {most} points")
-    _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
+def _check_cloud(t, name, most=None, device=None):
+    require(isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == 3 and t.shape[0] >= 1, f"{name} must be [N,3] with N >= 1")
+    check_tensor(t, name)
+    require(most is None or t.shape[0] <= most, f"{name} must have at most {most} points")
+    check_device(device, (t, name))
 
 
 def _check_transform(transform, device):
     """The [4,4] or [3,4] float32 device tensor whose first 12 floats the kernels read, or None."""
     if transform is None:
         return None
-    _require(isinstance(transform, torch.Tensor) and tuple(transform.shape) in ((4, 4), (3, 4)), "transform must be [4,4] or [3,4]")
-    _check_tensor(transform, "transform")
-    _require(transform.is_cuda and transform.device == device, f"transform must be a CUDA tensor on {device}")
+    require(isinstance(transform, torch.Tensor) and tuple(transform.shape) in ((4, 4), (3, 4)), "transform must be [4,4] or [3,4]")
+    check_tensor(transform, "transform")
+    check_device(device, (transform, "transform"))
     return transform
 
 
-def _check_vector(t, name, dtype, device, n=None, at_least=None):
-    """A contiguous 1-d tensor of `dtype` on `device` with exactly n, or at least `at_least`, elements."""
-    _require(isinstance(t, torch.Tensor) and t.dim() == 1, f"{name} must be a 1-d torch.Tensor")
-    _require(t.dtype == dtype, f"{name} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
-    _require(n is None or t.shape[0] == n, f"{name} must have {n} elements, got {tuple(t.shape)}")
-    _require(at_least is None or t.shape[0] >= at_least, f"{name} must have at least {at_least} elements, got {tuple(t.shape)}")
-    _require(t.is_contiguous(), f"{name} must be contiguous")
-    _require(t.is_cuda and (device is None or t.device == device), f"{name} must be a CUDA tensor" + (f" on {device}" if device else ""))
+def _check_vector(t, name, dtype, device, **length):
+    """check_vector, then the device, with the text this module has always refused a vector on another device with."""
+    check_vector(t, name, dtype, **length)
+    require(t.is_cuda and t.device == device, f"{name} must be a CUDA tensor on {device}")
 
 
 # -------------------------------------------------------------------------------------------------------------------- sampling
@@ -61,15 +57,15 @@ def sample_surface(vertices, triangles, n, seed=0):
     (points [n,3] float32, tri [n] int32, the triangle of each point).  Three launches and one host read (the total area, to
     refuse a mesh without area)."""
     _check_cloud(vertices, "vertices", 1 << 28)
-    _require(isinstance(triangles, torch.Tensor) and triangles.dim() == 2 and triangles.shape[1] == 3 and triangles.shape[0] >= 1,
-             "triangles must be [T,3] with T >= 1")
-    _require(triangles.dtype == torch.int32, f"triangles must be int32, got {triangles.dtype}")
-    _require(triangles.is_contiguous(), "triangles must be contiguous")
-    _require(triangles.shape[0] <= 1 << 28, "triangles must have at most 2^28 rows")
-    _require(triangles.is_cuda and triangles.device == vertices.device, f"triangles must be a CUDA tensor on {vertices.device}")
+    require(isinstance(triangles, torch.Tensor) and triangles.dim() == 2 and triangles.shape[1] == 3 and triangles.shape[0] >= 1,
+            "triangles must be [T,3] with T >= 1")
+    require(triangles.dtype == torch.int32, f"triangles must be int32, got {triangles.dtype}")
+    require(triangles.is_contiguous(), "triangles must be contiguous")
+    require(triangles.shape[0] <= 1 << 28, "triangles must have at most 2^28 rows")
+    check_device(vertices.device, (triangles, "triangles"))
     n, seed = int(n), int(seed)
-    _require(1 <= n <= MAX_SAMPLES, f"n must be in [1, 2^28], got {n}")
-    _require(0 <= seed < 1 << 32, "seed must be in [0, 2^32)")
+    require(1 <= n <= MAX_SAMPLES, f"n must be in [1, 2^28], got {n}")
+    require(0 <= seed < 1 << 32, "seed must be in [0, 2^32)")
     dev, T = vertices.device, int(triangles.shape[0])
     ws = torch.empty(_map_lib.lib().gs2d_recon_sample_ws_bytes(T), dtype=torch.uint8, device=dev)
     points = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -77,7 +73,7 @@ def sample_surface(vertices, triangles, n, seed=0):
     _map_lib.call("gs2d_recon_sample_surface", dev, int(vertices.shape[0]), vertices.data_ptr(), T, triangles.data_ptr(), n, seed,
                   ws.data_ptr(), points.data_ptr(), tri.data_ptr())
     area = float(ws[:8].view(torch.float64)[_map_lib.RECON_WS_TOTAL_AREA])
-    _require(area > 0.0 and math.isfinite(area), "the mesh has no area: no triangle with a finite area > 0 and indices inside [0, V)")
+    require(area > 0.0 and math.isfinite(area), "the mesh has no area: no triangle with a finite area > 0 and indices inside [0, V)")
     return points, tri
 
 
@@ -94,8 +90,7 @@ class PointGrid:
         _map_lib.call("gs2d_recon_grid_build", self.device, self.n, targets.data_ptr(), self.ws.data_ptr())
 
     def _check_queries(self, queries, transform):
-        _check_cloud(queries, "queries", (1 << 31) - 1)
-        _require(queries.device == self.device, f"queries must be on {self.device}")
+        _check_cloud(queries, "queries", (1 << 31) - 1, self.device)
         return _check_transform(transform, self.device)
 
     def nearest(self, queries, transform=None):
@@ -119,7 +114,7 @@ class PointGrid:
         _check_vector(dist, "dist", torch.float32, self.device, n=Q)
         _check_vector(index, "index", torch.int32, self.device, n=Q)
         thr = float(threshold)
-        _require(thr > 0 and math.isfinite(thr), "threshold must be > 0")
+        require(thr > 0 and math.isfinite(thr), "threshold must be > 0")
         if out is None:
             out = torch.empty(_map_lib.RECON_PAIR_DOUBLES, dtype=torch.float64, device=self.device)
         _check_vector(out, "out", torch.float64, self.device, at_least=_map_lib.RECON_PAIR_DOUBLES)
@@ -133,9 +128,9 @@ def distance_stats(dist, thr_a, thr_b, out=None):
     """gs2d_recon_distance_stats of dist [Q] float32 on the device: a float64 device tensor whose first RECON_STATS_VALUES entries are
     the number of finite distances, their sum, the sum of their squares, their maximum and the numbers below thr_a and thr_b.
     Sums are taken in a fixed order.  Two launches, no host read."""
-    _require(isinstance(dist, torch.Tensor) and dist.dim() == 1 and dist.shape[0] >= 1, "dist must be [Q] with Q >= 1")
-    _check_tensor(dist, "dist")
-    _require(dist.is_cuda, "dist must be a CUDA tensor (no CPU fallback)")
+    require(isinstance(dist, torch.Tensor) and dist.dim() == 1 and dist.shape[0] >= 1, "dist must be [Q] with Q >= 1")
+    check_tensor(dist, "dist")
+    check_device(None, (dist, "dist"))
     if out is None:
         out = torch.empty(_map_lib.RECON_STATS_DOUBLES, dtype=torch.float64, device=dist.device)
     _check_vector(out, "out", torch.float64, dist.device, at_least=_map_lib.RECON_STATS_DOUBLES)
@@ -166,8 +161,8 @@ def cloud_metrics(rec_points, gt_points, *, distance_thresh=0.01, ratio_thresh=0
     Two grids, two queries, two reductions and ONE host read at the end."""
     _check_cloud(rec_points, "rec_points", MAX_TARGETS)
     _check_cloud(gt_points, "gt_points", MAX_TARGETS)
-    _require(rec_points.device == gt_points.device, "both clouds must be on one device")
-    _require(float(distance_thresh) > 0 and float(ratio_thresh) > 0, "distance_thresh and ratio_thresh must be > 0")
+    require(rec_points.device == gt_points.device, "both clouds must be on one device")
+    require(float(distance_thresh) > 0 and float(ratio_thresh) > 0, "distance_thresh and ratio_thresh must be > 0")
     dev = rec_points.device
     transform = _check_transform(transform, dev)
     back = None
@@ -215,11 +210,11 @@ def icp_align(src, dst, *, threshold=0.1, max_iterations=30, relative_fitness=1e
     Returns (T [4,4] float64 numpy, fitness, inlier_rmse, iterations)."""
     _check_cloud(src, "src", (1 << 31) - 1)
     _check_cloud(dst, "dst", MAX_TARGETS)
-    _require(src.device == dst.device, "src and dst must be on one device")
-    _require(float(threshold) > 0 and math.isfinite(float(threshold)), "threshold must be > 0")
-    _require(int(max_iterations) >= 0, "max_iterations must be >= 0")
+    require(src.device == dst.device, "src and dst must be on one device")
+    require(float(threshold) > 0 and math.isfinite(float(threshold)), "threshold must be > 0")
+    require(int(max_iterations) >= 0, "max_iterations must be >= 0")
     T = np.eye(4) if init is None else np.array(init.detach().cpu() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
-    _require(T.shape == (4, 4) and np.isfinite(T).all(), "init must be a finite 4x4 matrix")
+    require(T.shape == (4, 4) and np.isfinite(T).all(), "init must be a finite 4x4 matrix")
     grid = PointGrid(dst)
     dev, N = src.device, int(src.shape[0])
     sums = torch.empty(_map_lib.RECON_PAIR_DOUBLES, dtype=torch.float64, device=dev)
@@ -258,10 +253,10 @@ def evaluate_reconstruction(vertices, triangles, gt_vertices, gt_triangles=None,
     float64), `icp_fitness` and `icp_rmse` (None without align)."""
     _check_cloud(vertices, "vertices", 1 << 28)
     _check_cloud(gt_vertices, "gt_vertices", MAX_TARGETS if gt_triangles is None else 1 << 28)
-    _require(gt_vertices.device == vertices.device, "the two meshes must be on one device")
-    _require(float(icp_threshold) > 0 and float(distance_thresh) > 0 and float(ratio_thresh) > 0,
-             "icp_threshold, distance_thresh and ratio_thresh must be > 0")
-    _require(1 <= int(n_samples) <= MAX_TARGETS, f"n_samples must be in [1, 2^27] (both clouds become grids), got {n_samples}")
+    require(gt_vertices.device == vertices.device, "the two meshes must be on one device")
+    require(float(icp_threshold) > 0 and float(distance_thresh) > 0 and float(ratio_thresh) > 0,
+            "icp_threshold, distance_thresh and ratio_thresh must be > 0")
+    require(1 <= int(n_samples) <= MAX_TARGETS, f"n_samples must be in [1, 2^27] (both clouds become grids), got {n_samples}")
     rec = sample_surface(vertices, triangles, n_samples, seed)[0]
     gt = gt_vertices if gt_triangles is None else sample_surface(gt_vertices, gt_triangles, n_samples, seed + 1)[0]
     T, fitness, rmse = np.eye(4), None, None

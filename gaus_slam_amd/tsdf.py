@@ -22,7 +22,7 @@ import math
 import torch
 
 from . import _map_lib
-from .densify import _check_tensor, _require
+from ._check import check_device, check_tensor, require
 
 MAX_VOXELS = (1 << 31) - 1
 
@@ -30,23 +30,23 @@ MAX_VOXELS = (1 << 31) - 1
 def _intrinsics4(intrinsics):
     """(fx, fy, cx, cy) as Python floats from four host numbers or a [3,3] matrix."""
     if isinstance(intrinsics, torch.Tensor):
-        _require(not intrinsics.is_cuda, "intrinsics must be host values: a device tensor would cost a host read per frame")
+        require(not intrinsics.is_cuda, "intrinsics must be host values: a device tensor would cost a host read per frame")
         intrinsics = intrinsics.detach().tolist()
     k = [list(r) if hasattr(r, "__len__") else r for r in list(intrinsics)]
     if len(k) == 3 and all(isinstance(r, list) and len(r) == 3 for r in k):
         vals = (k[0][0], k[1][1], k[0][2], k[1][2])
     else:
-        _require(len(k) == 4 and not any(isinstance(r, list) for r in k), "intrinsics must be (fx, fy, cx, cy) or a 3x3 matrix")
+        require(len(k) == 4 and not any(isinstance(r, list) for r in k), "intrinsics must be (fx, fy, cx, cy) or a 3x3 matrix")
         vals = k
     fx, fy, cx, cy = (float(x) for x in vals)
-    _require(fx != 0.0 and fy != 0.0 and all(math.isfinite(x) for x in (fx, fy, cx, cy)), "intrinsics must be finite with fx, fy != 0")
+    require(fx != 0.0 and fy != 0.0 and all(math.isfinite(x) for x in (fx, fy, cx, cy)), "intrinsics must be finite with fx, fy != 0")
     return fx, fy, cx, cy
 
 
 def bounds_of_map(means3D, margin=0.0):
     """(lo, hi), each three Python floats: the bounding box of the Gaussian centres grown by `margin`.  One host read."""
-    _require(isinstance(means3D, torch.Tensor) and means3D.dim() == 2 and means3D.shape[1] == 3 and means3D.shape[0] >= 1,
-             "means3D must be [P,3] with P >= 1")
+    require(isinstance(means3D, torch.Tensor) and means3D.dim() == 2 and means3D.shape[1] == 3 and means3D.shape[0] >= 1,
+            "means3D must be [P,3] with P >= 1")
     lo, hi = torch.aminmax(means3D.detach(), dim=0)
     both = torch.cat([lo, hi]).to("cpu", torch.float64).tolist()
     m = float(margin)
@@ -61,14 +61,14 @@ class TSDFVolume:
     def __init__(self, origin, dims, voxel_length=5.0 / 512.0, sdf_trunc=0.04, depth_trunc=30.0, device="cuda"):
         self.origin = tuple(float(x) for x in origin)
         self.dims = tuple(int(x) for x in dims)
-        _require(len(self.origin) == 3 and len(self.dims) == 3, "origin and dims must have three entries")
-        _require(all(math.isfinite(x) for x in self.origin), "origin must be finite")
-        _require(min(self.dims) >= 2, f"every axis of the volume must have at least 2 voxels, got {self.dims}")
+        require(len(self.origin) == 3 and len(self.dims) == 3, "origin and dims must have three entries")
+        require(all(math.isfinite(x) for x in self.origin), "origin must be finite")
+        require(min(self.dims) >= 2, f"every axis of the volume must have at least 2 voxels, got {self.dims}")
         nx, ny, nz = self.dims
-        _require(nx * ny * nz <= MAX_VOXELS, f"the volume must have fewer than 2^31 voxels, got {nx}x{ny}x{nz}")
+        require(nx * ny * nz <= MAX_VOXELS, f"the volume must have fewer than 2^31 voxels, got {nx}x{ny}x{nz}")
         self.voxel_length, self.sdf_trunc, self.depth_trunc = float(voxel_length), float(sdf_trunc), float(depth_trunc)
-        _require(self.voxel_length > 0 and self.sdf_trunc > 0 and self.depth_trunc > 0,
-                 "voxel_length, sdf_trunc and depth_trunc must be > 0")
+        require(self.voxel_length > 0 and self.sdf_trunc > 0 and self.depth_trunc > 0,
+                "voxel_length, sdf_trunc and depth_trunc must be > 0")
         self.device = torch.device(device)
         self.planes = torch.zeros((5, nz, ny, nx), dtype=torch.float32, device=self.device)
         self.tsdf, self.weight, self.color = self.planes[0], self.planes[1], self.planes[2:5]
@@ -77,8 +77,8 @@ class TSDFVolume:
     def from_bounds(cls, lo, hi, voxel_length=5.0 / 512.0, **kw):
         """The smallest volume of whole voxels, on the lattice of multiples of voxel_length, that contains the box [lo, hi]."""
         L = float(voxel_length)
-        _require(L > 0, "voxel_length must be > 0")
-        _require(all(float(h) > float(l) for l, h in zip(lo, hi)), "hi must exceed lo on every axis")
+        require(L > 0, "voxel_length must be > 0")
+        require(all(float(h) > float(l) for l, h in zip(lo, hi)), "hi must exceed lo on every axis")
         first = [math.floor(float(l) / L) for l in lo]
         last = [math.ceil(float(h) / L) for h in hi]
         return cls([f * L for f in first], [max(2, b - a) for a, b in zip(first, last)], voxel_length=L, **kw)
@@ -88,17 +88,15 @@ class TSDFVolume:
 
     # ------------------------------------------------------------------------------------------------------------- integrate
     def _check_frame(self, color, depth, depth_shape, depth_name, w2c):
-        _require(isinstance(depth, torch.Tensor) and depth.dim() == len(depth_shape) and
-                 all(s is None or int(depth.shape[i]) == s for i, s in enumerate(depth_shape)),
-                 f"{depth_name} must be {'[7,H,W], the raw rasterizer output' if len(depth_shape) == 3 else '[H,W]'}")
+        require(isinstance(depth, torch.Tensor) and depth.dim() == len(depth_shape) and
+                all(s is None or int(depth.shape[i]) == s for i, s in enumerate(depth_shape)),
+                f"{depth_name} must be {'[7,H,W], the raw rasterizer output' if len(depth_shape) == 3 else '[H,W]'}")
         H, W = int(depth.shape[-2]), int(depth.shape[-1])
-        _require(H >= 1 and W >= 1 and H * W <= 1 << 30, f"{depth_name} must have 1 <= H*W <= 2^30 pixels")
-        _check_tensor(depth, depth_name)
-        _check_tensor(color, "color", shape=(3, H, W))
-        _check_tensor(w2c, "w2c", shape=(4, 4))
-        for t, name in ((self.planes, "the volume"), (color, "color"), (depth, depth_name), (w2c, "w2c")):
-            _require(t.is_cuda, f"{name} must be a CUDA tensor (no CPU fallback)")
-            _require(t.device == self.planes.device, f"{name} must be on {self.planes.device}")
+        require(H >= 1 and W >= 1 and H * W <= 1 << 30, f"{depth_name} must have 1 <= H*W <= 2^30 pixels")
+        check_tensor(depth, depth_name)
+        check_tensor(color, "color", shape=(3, H, W))
+        check_tensor(w2c, "w2c", shape=(4, 4))
+        check_device(self.planes.device, (self.planes, "the volume"), (color, "color"), (depth, depth_name), (w2c, "w2c"))
         return W, H
 
     def _integrate(self, W, H, color, depth, is_allmap, cfg, intrinsics, w2c, rgb8):
@@ -131,10 +129,10 @@ class TSDFVolume:
         """The zero level set by marching tetrahedra: (vertices [V,3] float32, colors [V,3] float32 in [0, 1], triangles [T,3]
         int32) on the device, in the order include/gs2d_tsdf.h fixes, normals toward free space.  Only cubes whose eight
         corners were observed (weight > 0) produce triangles.  One host read: the two counts."""
-        _require(self.planes.is_cuda, "the volume must be a CUDA tensor (no CPU fallback)")
+        check_device(None, (self.planes, "the volume"))
         lib, p, dev = _map_lib.lib(), self.planes, self.planes.device
         nbytes = lib.gs2d_tsdf_extract_ws_bytes(*self.dims)
-        _require(nbytes > 0, f"extraction takes at most 2^28 voxels, got {self.dims}")
+        require(nbytes > 0, f"extraction takes at most 2^28 voxels, got {self.dims}")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         _map_lib.call("gs2d_tsdf_extract_count", dev, *self.dims, p[0].data_ptr(), p[1].data_ptr(), ws.data_ptr())
         counts = ws[:8].view(torch.int32).cpu()

@@ -1,10 +1,19 @@
-"""Synthetic inputs that more than one map-side GPU test module uses."""
+"""What more than one map-side test module uses: synthetic inputs, and the fixture that builds and binds the map library."""
 import math
 
 import numpy as np
+import pytest
 import torch
 
 F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def maplib():
+    """The map library, built if stale and bound (import the name into a test module to use it)."""
+    from gaus_slam_amd import build, _map_lib
+    build.build()
+    return _map_lib.lib()
 
 
 def _rot(axis, deg):

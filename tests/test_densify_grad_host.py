@@ -9,17 +9,11 @@ import pytest
 import torch
 
 from tests import densify_grad_ref as ref
+from tests.map_inputs import maplib  # noqa: F401  (the fixture: the built and bound map library)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["gs2d_map_densify_stats", "gs2d_map_densify_ws_bytes", "gs2d_map_densify_select", "gs2d_map_densify_write"]
 CFG = dict(densify_grad_threshold=2e-4, percent_dense=0.01, extent=2.0, opacity_cuil=0.05, scale_cuil=5e-4, scale_max=0.1)
-
-
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
 
 
 def test_header_declares_and_binding_prototypes_the_new_entries(maplib):

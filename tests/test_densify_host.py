@@ -1,33 +1,11 @@
-"""CPU tests of the map growth / pruning layer: the second library cross-compiles and exports its C ABI, the building blocks of
-the PyTorch restatement (tests/densify_ref.py) agree with the reference's literal statements, and the Python entry points
-reject what they do not support.  Nothing here launches a kernel."""
-import os
-import re
-
+"""CPU tests of the map growth / pruning layer: the second library cross-compiles for gfx950 with its own hash (its C ABI:
+tests/test_abi_host.py), the building blocks of the PyTorch restatement (tests/densify_ref.py) agree with the reference's
+literal statements, and the Python entry points reject what they do not support.  Nothing here launches a kernel."""
 import pytest
 import torch
 
 from tests import densify_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
-
-
-def test_map_library_exports_every_declared_symbol(maplib):
-    from gaus_slam_amd import _map_lib
-    hdr = open(os.path.join(ROOT, "include", "gs2d_map.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(gs2d_map_[a-z0-9_]+)\s*\(", hdr))
-    assert {"gs2d_map_seed_select", "gs2d_map_seed_write", "gs2d_map_prune_select", "gs2d_map_compact"} <= names
-    for n in sorted(names):
-        assert hasattr(maplib, n), n
-    assert set(_map_lib.EXPORTS) == names
+from tests.map_inputs import maplib  # noqa: F401  (the fixture: the built and bound map library)
 
 
 def test_map_library_is_a_gfx950_code_object_with_its_own_hash(maplib):
@@ -37,14 +15,6 @@ def test_map_library_is_a_gfx950_code_object_with_its_own_hash(maplib):
     assert _map_lib.lib_source_hash() == build.map_source_hash(), _map_lib.build_info()
     assert "fp-contract=off" in _map_lib.build_info()
     assert "-ffp-contract=off" in build.FLAGS  # selection is only exact without contraction
-
-
-def test_map_sources_stay_out_of_the_rasterizer_hash():
-    """The kept rasterizer profiles are tied to build.source_hash(): it must cover csrc/ and gs2d_rasterizer.h only."""
-    from gaus_slam_amd import build
-    assert os.path.realpath(build.CSRC_MAP) != os.path.realpath(build.CSRC)
-    assert not [f for f in os.listdir(build.CSRC) if "map" in f]
-    assert build.map_source_hash() != build.source_hash()
 
 
 def test_workspace_sizes(maplib):

@@ -1,6 +1,6 @@
-"""CPU tests of the evaluation layer: the map library exports the C ABI of include/gs2d_eval.h, build and binding know the
-header, the PyTorch restatement (tests/eval_ref.py) has the properties the published definitions give it, ate_rmse aligns as
-evo does, and frame_metrics rejects what it does not support.  Nothing here launches a kernel."""
+"""CPU tests of the evaluation layer: the PyTorch restatement (tests/eval_ref.py) has the properties the published definitions
+give it, ate_rmse aligns as evo does, and frame_metrics rejects what it does not support (the C ABI of include/gs2d_eval.h:
+tests/test_abi_host.py).  Nothing here launches a kernel."""
 import os
 import re
 
@@ -9,48 +9,13 @@ import pytest
 import torch
 
 from tests import eval_ref as ref
+from tests.map_inputs import maplib  # noqa: F401  (the fixture: the built and bound map library)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
-
-
 def _header():
     return open(os.path.join(ROOT, "include", "gs2d_eval.h")).read()
-
-
-def test_map_library_exports_every_declared_eval_symbol(maplib):
-    from gaus_slam_amd import _map_lib
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    names = set(re.findall(r"\b(gs2d_eval_[a-z0-9_]+)\s*\(", hdr))
-    assert names == {"gs2d_eval_ws_bytes", "gs2d_eval_frame"}
-    for n in sorted(names):
-        assert hasattr(maplib, n), n
-    assert set(_map_lib.EVAL_EXPORTS) == names
-    assert not set(_map_lib.EVAL_EXPORTS) & (set(_map_lib.EXPORTS) | set(_map_lib.POSE_EXPORTS))
-    assert all(n.startswith("gs2d_eval_") for n in _map_lib.EVAL_EXPORTS)
-
-
-def test_eval_source_is_in_the_map_library_only():
-    from gaus_slam_amd import build, _map_lib
-    assert "gs2d_eval.hip" in build.MAP_SOURCES and os.path.exists(os.path.join(build.CSRC_MAP, "gs2d_eval.hip"))
-    assert not [f for f in os.listdir(build.CSRC) if "eval" in f]
-    assert _map_lib.lib_source_hash() == build.map_source_hash(), _map_lib.build_info()
-
-
-def test_map_hash_and_staleness_cover_the_eval_header(tmp_path, monkeypatch):
-    from gaus_slam_amd import build
-    before = build.map_source_hash()
-    copy = tmp_path / "gs2d_eval.h"
-    copy.write_bytes(open(build.EVAL_HEADER, "rb").read() + b"\n")
-    monkeypatch.setattr(build, "EVAL_HEADER", str(copy))
-    assert build.map_source_hash() != before
-    assert build._map_stale()
 
 
 def test_binding_and_helper_mirror_the_header_constants():

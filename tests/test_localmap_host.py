@@ -10,16 +10,10 @@ import pytest
 import torch
 
 from tests import localmap_ref as ref
+from tests.map_inputs import maplib  # noqa: F401  (the fixture: the built and bound map library)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAP = -4.59511995  # any float32 logit: the inputs only have to sit below, on and above it
-
-
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
 
 
 def test_merge_is_exported_and_mode_all_is_declared(maplib):

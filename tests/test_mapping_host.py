@@ -7,13 +7,7 @@ import pytest
 import torch
 
 from tests import mapping_ref as ref
-
-
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
+from tests.map_inputs import maplib  # noqa: F401  (the fixture: the built and bound map library)
 
 
 def _f64_case(P=4099):

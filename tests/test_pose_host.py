@@ -1,6 +1,6 @@
-"""CPU tests of the pose optimiser layer: the map library exports the C ABI of include/gs2d_pose.h, the pieces of the PyTorch
-restatement (tests/pose_ref.py) behave as the reference states them, the closed-form quaternion gradient of the step kernel
-equals autograd, and the Python entry points reject what they do not support.  Nothing here launches a kernel."""
+"""CPU tests of the pose optimiser layer: the pieces of the PyTorch restatement (tests/pose_ref.py) behave as the reference
+states them, the closed-form quaternion gradient of the step kernel equals autograd, and the Python entry points reject what
+they do not support (the C ABI of include/gs2d_pose.h: tests/test_abi_host.py).  Nothing here launches a kernel."""
 import os
 import re
 
@@ -10,42 +10,6 @@ import torch
 from tests import pose_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
-
-
-def test_map_library_exports_every_declared_pose_symbol(maplib):
-    from gaus_slam_amd import _map_lib
-    hdr = open(os.path.join(ROOT, "include", "gs2d_pose.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(gs2d_pose_[a-z0-9_]+)\s*\(", hdr))
-    assert {"gs2d_pose_init", "gs2d_pose_step", "gs2d_pose_frame_stats"} <= names
-    for n in sorted(names):
-        assert hasattr(maplib, n), n
-    assert set(_map_lib.POSE_EXPORTS) == names
-    assert not set(_map_lib.POSE_EXPORTS) & set(_map_lib.EXPORTS)
-
-
-def test_pose_sources_are_in_the_map_library_only():
-    from gaus_slam_amd import build, _map_lib
-    assert "gs2d_pose.hip" in build.MAP_SOURCES and os.path.exists(os.path.join(build.CSRC_MAP, "gs2d_pose.hip"))
-    assert not [f for f in os.listdir(build.CSRC) if "pose" in f]
-    assert _map_lib.lib_source_hash() == build.map_source_hash(), _map_lib.build_info()
-
-
-def test_map_hash_and_staleness_cover_the_pose_header(tmp_path, monkeypatch):
-    from gaus_slam_amd import build
-    before = build.map_source_hash()
-    copy = tmp_path / "gs2d_pose.h"
-    copy.write_bytes(open(build.POSE_HEADER, "rb").read() + b"\n")
-    monkeypatch.setattr(build, "POSE_HEADER", str(copy))
-    assert build.map_source_hash() != before
-    assert build._map_stale()
 
 
 def test_binding_mirrors_the_header_constants():

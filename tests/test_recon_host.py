@@ -1,5 +1,5 @@
-"""CPU tests of the reconstruction metrics: the map library exports the C ABI of include/gs2d_recon.h, build and binding know the
-header and the source, the library and the Python layer refuse what they do not support before anything is launched, and the
+"""CPU tests of the reconstruction metrics (the C ABI of include/gs2d_recon.h: tests/test_abi_host.py): the
+library and the Python layer refuse what they do not support before anything is launched, and the
 yardstick (tests/recon_ref.py) checks itself in float64: stratified counts, points inside their triangles, brute force against
 a k-d tree, and an ICP that recovers a known motion.  Nothing here launches a kernel."""
 import os
@@ -11,43 +11,16 @@ import torch
 
 from gaus_slam_amd import recon as _feature  # noqa: F401  (every test here is about this module, the yardstick's checks included)
 from tests import recon_ref as ref
+from tests.map_inputs import maplib  # noqa: F401  (the fixture: the built and bound map library)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"gs2d_recon_sample_ws_bytes", "gs2d_recon_sample_surface", "gs2d_recon_grid_ws_bytes", "gs2d_recon_grid_build",
-         "gs2d_recon_nearest", "gs2d_recon_distance_stats", "gs2d_recon_pair_sums"}
-
-
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
 
 
 def _header():
     return open(os.path.join(ROOT, "include", "gs2d_recon.h")).read()
 
 
-# ------------------------------------------------------------------------------------------------------------ build and binding
-def test_map_library_exports_exactly_the_declared_recon_symbols(maplib):
-    from gaus_slam_amd import _map_lib
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    names = set(re.findall(r"\b(gs2d_recon_[a-z0-9_]+)\s*\(", hdr))
-    assert names == NAMES
-    for n in sorted(names):
-        assert hasattr(maplib, n), n
-    import shutil
-    import subprocess
-    if shutil.which("nm"):  # the dynamic symbol table: nothing else carries the prefix
-        nm = subprocess.run(["nm", "-D", "--defined-only", _map_lib._build.MAP_LIB_PATH], capture_output=True, text=True)
-        if nm.returncode == 0:
-            assert set(re.findall(r"\b(gs2d_recon_[a-z0-9_]+)\b", nm.stdout)) == names
-    assert set(_map_lib.RECON_EXPORTS) == names and len(_map_lib.RECON_EXPORTS) == len(names)
-    others = set(_map_lib.EXPORTS) | set(_map_lib.POSE_EXPORTS) | set(_map_lib.EVAL_EXPORTS) | set(_map_lib.TSDF_EXPORTS)
-    assert not set(_map_lib.RECON_EXPORTS) & others
-    assert not [n for n in _map_lib.RECON_EXPORTS if n.startswith("gs2d_eval_")]
-
-
+# ------------------------------------------------------------------------------------------------------------------ the library
 def test_constants_mirror_the_header():
     from gaus_slam_amd import _map_lib
     defs = {k: int(v) for k, v in re.findall(r"#define GS2D_RECON_([A-Z0-9_]+) +(\d+)", _header())}
@@ -57,24 +30,6 @@ def test_constants_mirror_the_header():
     assert defs["STATS_DOUBLES"] == defs["STATS_VALUES"] * 257 and defs["PAIR_DOUBLES"] == defs["PAIR_VALUES"] * 257
     assert sorted(defs[k] for k in defs if k.startswith("STATS_") and k not in ("STATS_VALUES", "STATS_DOUBLES")) == list(range(6))
     assert (defs["PAIR_N"], defs["PAIR_P"], defs["PAIR_Q"], defs["PAIR_PQ"], defs["PAIR_D2"], defs["PAIR_VALUES"]) == (0, 1, 4, 7, 16, 17)
-
-
-def test_recon_source_is_in_the_map_library_only():
-    from gaus_slam_amd import build, _map_lib
-    assert "gs2d_recon.hip" in build.MAP_SOURCES and os.path.exists(os.path.join(build.CSRC_MAP, "gs2d_recon.hip"))
-    assert not [f for f in os.listdir(build.CSRC) if "recon" in f]
-    build.build()
-    assert _map_lib.lib_source_hash() == build.map_source_hash(), _map_lib.build_info()
-
-
-def test_map_hash_and_staleness_cover_the_recon_header(tmp_path, monkeypatch):
-    from gaus_slam_amd import build
-    before = build.map_source_hash()
-    copy = tmp_path / "gs2d_recon.h"
-    copy.write_bytes(open(build.RECON_HEADER, "rb").read() + b"\n")
-    monkeypatch.setattr(build, "RECON_HEADER", str(copy))
-    assert build.map_source_hash() != before
-    assert build._map_stale()
 
 
 def test_workspace_sizes_need_no_host_read(maplib):

@@ -1,26 +1,14 @@
-"""CPU tests of the TSDF layer: the map library exports the C ABI of include/gs2d_tsdf.h, build and binding know the header and
-the source, the library's table of tetrahedron cases equals what tests/tsdf_ref.py derives from geometry, the Python layer
-rejects what it does not support before any library call, meshes round-trip through the PLY writer, and the yardstick checks
-itself: the reference's meshes of analytic shapes have the topology and orientation those shapes have, and its float32 and
-float64 evaluations take different decisions only on flagged voxels.  Nothing here launches a kernel."""
-import os
-import re
-
+"""CPU tests of the TSDF layer: the library refuses bad arguments before it launches (the C ABI of include/gs2d_tsdf.h itself:
+tests/test_abi_host.py), the library's table of tetrahedron cases equals what tests/tsdf_ref.py derives from geometry, the
+Python layer rejects what it does not support before any library call, meshes round-trip through the PLY writer, and the
+yardstick checks itself: the reference's meshes of analytic shapes have the topology and orientation those shapes have, and
+its float32 and float64 evaluations take different decisions only on flagged voxels.  Nothing here launches a kernel."""
 import numpy as np
 import pytest
 import torch
 
 from tests import tsdf_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"gs2d_tsdf_integrate", "gs2d_tsdf_extract_ws_bytes", "gs2d_tsdf_extract_count", "gs2d_tsdf_extract_write", "gs2d_tsdf_tet_case"}
-
-
-@pytest.fixture(scope="module")
-def maplib():
-    from gaus_slam_amd import build, _map_lib
-    build.build()
-    return _map_lib.lib()
+from tests.map_inputs import maplib  # noqa: F401  (the fixture: the built and bound map library)
 
 
 @pytest.fixture(scope="module")
@@ -33,42 +21,7 @@ def meshes():
     return out
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "gs2d_tsdf.h")).read()
-
-
-# ------------------------------------------------------------------------------------------------------------ build and binding
-def test_map_library_exports_every_declared_tsdf_symbol(maplib):
-    from gaus_slam_amd import _map_lib
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    names = set(re.findall(r"\b(gs2d_tsdf_[a-z0-9_]+)\s*\(", hdr))
-    assert names == NAMES
-    for n in sorted(names):
-        assert hasattr(maplib, n), n
-    assert set(_map_lib.TSDF_EXPORTS) == names and len(_map_lib.TSDF_EXPORTS) == len(names)
-    assert not set(_map_lib.TSDF_EXPORTS) & (set(_map_lib.EXPORTS) | set(_map_lib.POSE_EXPORTS) | set(_map_lib.EVAL_EXPORTS))
-    defs = {k: int(v) for k, v in re.findall(r"#define GS2D_TSDF_WS_([A-Z]+) +(\d+)", _header())}
-    assert defs == {"VERTICES": _map_lib.TSDF_WS_VERTICES, "TRIANGLES": _map_lib.TSDF_WS_TRIANGLES}
-    assert defs["VERTICES"] != defs["TRIANGLES"]
-
-
-def test_tsdf_source_is_in_the_map_library_only():
-    from gaus_slam_amd import build, _map_lib
-    assert "gs2d_tsdf.hip" in build.MAP_SOURCES and os.path.exists(os.path.join(build.CSRC_MAP, "gs2d_tsdf.hip"))
-    assert not [f for f in os.listdir(build.CSRC) if "tsdf" in f]
-    assert _map_lib.lib_source_hash() == build.map_source_hash(), _map_lib.build_info()
-
-
-def test_map_hash_and_staleness_cover_the_tsdf_header(tmp_path, monkeypatch):
-    from gaus_slam_amd import build
-    before = build.map_source_hash()
-    copy = tmp_path / "gs2d_tsdf.h"
-    copy.write_bytes(open(build.TSDF_HEADER, "rb").read() + b"\n")
-    monkeypatch.setattr(build, "TSDF_HEADER", str(copy))
-    assert build.map_source_hash() != before
-    assert build._map_stale()
-
-
+# ------------------------------------------------------------------------------------------------------------------ the library
 def test_extract_workspace_size_and_refused_dims(maplib):
     ws = maplib.gs2d_tsdf_extract_ws_bytes
     for dims in ((1, 8, 8), (8, 1, 8), (8, 8, 1), (0, 4, 4), (4, -2, 4), (1 << 10, 1 << 10, 257), (1 << 16, 1 << 16, 2)):
