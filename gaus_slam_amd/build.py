@@ -1,7 +1,8 @@
-"""Builds the gfx950 shared libraries with hipcc: the rasterizer library (C ABI in include/gs2d_rasterizer.h) and the map
+"""Builds the gfx950 shared libraries with hipcc: the rasterizer library (C ABI in include/gs2d_rasterizer.h), the map
 growth / pruning library, which also holds the camera pose optimiser, the evaluation metrics, the TSDF volume and the
 reconstruction metrics (C ABI in include/gs2d_map.h, include/gs2d_pose.h, include/gs2d_eval.h, include/gs2d_tsdf.h and
-include/gs2d_recon.h, sources in csrc_map/).
+include/gs2d_recon.h, sources in csrc_map/), and the mesh library: the triangle-mesh depth renderer with Depth L1 and clean_mesh
+(C ABI in include/gs2d_mesh.h, sources in csrc_mesh/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -30,6 +31,12 @@ MAP_SOURCES = ["gs2d_map.hip", "gs2d_map_densify.hip", "gs2d_pose.hip", "gs2d_ma
 # the map library's C-ABI headers, in the order map_source_hash() hashes them
 MAP_HEADERS = [os.path.join(_HERE, "..", "include", f) for f in ("gs2d_map.h", "gs2d_pose.h", "gs2d_eval.h", "gs2d_tsdf.h", "gs2d_recon.h")]
 RASTERIZER_HEADER = os.path.join(_HERE, "..", "include", "gs2d_rasterizer.h")
+
+# The mesh renderer is a third library for the same reason: neither of the two hashes above moves with it.
+CSRC_MESH = os.path.join(_HERE, "csrc_mesh")
+MESH_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_mesh_hip.so")
+MESH_SOURCES = ["gs2d_mesh.hip"]
+MESH_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_mesh.h")]
 
 
 def _hash(directory, headers):
@@ -101,9 +108,28 @@ def build_map(force=False, verbose=False):
     return _compile(MAP_LIB_PATH, [os.path.join(CSRC_MAP, f) for f in MAP_SOURCES], "GS2D_MAP_SOURCE_HASH", map_source_hash(), verbose)
 
 
+def mesh_source_hash():
+    """source_hash() of the mesh library: every file under csrc_mesh/ plus MESH_HEADERS (gs2d_mesh_build_info reports it)."""
+    return _hash(CSRC_MESH, MESH_HEADERS)
+
+
+def _mesh_stale():
+    """Like the map library, the mesh library includes ../csrc/gs2d_scan.h and gs2d_common.h."""
+    deps = [os.path.join(CSRC_MESH, f) for f in os.listdir(CSRC_MESH)] + MESH_HEADERS + [os.path.join(CSRC, "gs2d_scan.h"),
+                                                                                         os.path.join(CSRC, "gs2d_common.h")]
+    return _is_stale(MESH_LIB_PATH, mesh_source_hash(), deps)
+
+
+def build_mesh(force=False, verbose=False):
+    if not force and not _mesh_stale():
+        return MESH_LIB_PATH
+    return _compile(MESH_LIB_PATH, [os.path.join(CSRC_MESH, f) for f in MESH_SOURCES], "GS2D_MESH_SOURCE_HASH", mesh_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds both libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the three libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
+    build_mesh(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -114,3 +140,4 @@ if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     print(LIB_PATH)
     print(MAP_LIB_PATH)
+    print(MESH_LIB_PATH)

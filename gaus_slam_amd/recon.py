@@ -10,8 +10,8 @@ claimed: the sampler, the alignment and the metrics follow the published definit
     res = evaluate_reconstruction(vertices, triangles, gt_vertices, gt_triangles)
     res["accuracy"], res["completion"], res["completion_ratio"], res["fscore"], res["transform"]
 
-Out of scope: clean_mesh (dropping connected components under 200 vertices, the natural next step), calc_2d_metric (needs a
-mesh renderer), reading the *_pc_unseen.npy culling file, and LPIPS.
+Out of scope here: clean_mesh and calc_2d_metric (Depth L1), which gaus_slam_amd/meshrender.py does with a mesh depth renderer of
+its own (meshrender.evaluate_mesh runs them around evaluate_reconstruction), and LPIPS.
 
 No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError before any library call."""
 import math
