@@ -1,8 +1,9 @@
 """Builds the gfx950 shared libraries with hipcc: the rasterizer library (C ABI in include/gs2d_rasterizer.h), the map
 growth / pruning library, which also holds the camera pose optimiser, the evaluation metrics, the TSDF volume and the
 reconstruction metrics (C ABI in include/gs2d_map.h, include/gs2d_pose.h, include/gs2d_eval.h, include/gs2d_tsdf.h and
-include/gs2d_recon.h, sources in csrc_map/), and the mesh library: the triangle-mesh depth renderer with Depth L1 and clean_mesh
-(C ABI in include/gs2d_mesh.h, sources in csrc_mesh/).
+include/gs2d_recon.h, sources in csrc_map/), the mesh library: the triangle-mesh depth renderer with Depth L1 and clean_mesh
+(C ABI in include/gs2d_mesh.h, sources in csrc_mesh/), and the loss library: the fused SLAM loss with exposure and the tracking
+outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources in csrc_loss/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -37,6 +38,13 @@ CSRC_MESH = os.path.join(_HERE, "csrc_mesh")
 MESH_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_mesh_hip.so")
 MESH_SOURCES = ["gs2d_mesh.hip"]
 MESH_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_mesh.h")]
+
+# The extended loss is a fourth library, again for the hashes' sake: it restates the per-pixel terms of csrc/gs2d_loss.hip, which
+# cannot change without moving source_hash().  It includes nothing of csrc/.
+CSRC_LOSS = os.path.join(_HERE, "csrc_loss")
+LOSS_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_loss_hip.so")
+LOSS_SOURCES = ["gs2d_loss_ex.hip"]
+LOSS_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_loss.h")]
 
 
 def _hash(directory, headers):
@@ -126,10 +134,27 @@ def build_mesh(force=False, verbose=False):
     return _compile(MESH_LIB_PATH, [os.path.join(CSRC_MESH, f) for f in MESH_SOURCES], "GS2D_MESH_SOURCE_HASH", mesh_source_hash(), verbose)
 
 
+def loss_source_hash():
+    """source_hash() of the loss library: every file under csrc_loss/ plus LOSS_HEADERS (gs2d_loss_build_info reports it)."""
+    return _hash(CSRC_LOSS, LOSS_HEADERS)
+
+
+def _loss_stale():
+    deps = [os.path.join(CSRC_LOSS, f) for f in os.listdir(CSRC_LOSS)] + LOSS_HEADERS
+    return _is_stale(LOSS_LIB_PATH, loss_source_hash(), deps)
+
+
+def build_loss(force=False, verbose=False):
+    if not force and not _loss_stale():
+        return LOSS_LIB_PATH
+    return _compile(LOSS_LIB_PATH, [os.path.join(CSRC_LOSS, f) for f in LOSS_SOURCES], "GS2D_LOSS_SOURCE_HASH", loss_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the three libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the four libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
+    build_loss(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -141,3 +166,4 @@ if __name__ == "__main__":
     print(LIB_PATH)
     print(MAP_LIB_PATH)
     print(MESH_LIB_PATH)
+    print(LOSS_LIB_PATH)

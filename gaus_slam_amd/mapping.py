@@ -1,4 +1,4 @@
-"""The mapping iteration from RAW parameters.
+"""The mapping iteration from RAW parameters (the exposure parameters: section 7.10).
 
 The reference stores opacity logits, log scales and unnormalised quaternions, activates them on every render
 (`Gaussians.get_render_params`, scene/Gaussians.py:299-347: sigmoid / exp / F.normalize) and lets
@@ -14,7 +14,7 @@ so no activation is an autograd node, the operator still sees leaves (`direct_gr
 map stays in the storage `densify.add_new_gaussians` / `prune_gaussians` / `densify_and_prune` expect (`activated=False`).
 `map_frames` is the loop of Frontend.mapping / Backend.mapping on top of it.
 
-Not covered: isotropic Gaussians (one log scale per row), SH colours, the exposure parameters, and densification statistics
+Not covered: isotropic Gaussians (one log scale per row), SH colours, and densification statistics
 fused into the step (`DensificationStats.add` stays a launch of its own).  No CPU fallback: CPU tensors raise RuntimeError."""
 import ctypes as C
 import random
@@ -128,7 +128,7 @@ class RawGaussianAdam(FusedGaussianAdam):
 
 
 def map_frames(opt, frames, num_iters, w_color, w_depth, w_dist, *, order=None, stats=None, densify_cfg=None, densify_interval=0,
-               generator=None, **loss_kwargs):
+               generator=None, exposures=None, exposure_after=10, **loss_kwargs):
     """The loop of Frontend.mapping / Backend.mapping (slam/Frontend.py, slam/Backend.py:101-128) on a RawGaussianAdam.
 
     frames: a list of (settings, gt_color [H,W,3], gt_depth [H,W] or [H,W,1]); order: the frame index of every iteration -- the
@@ -137,6 +137,12 @@ def map_frames(opt, frames, num_iters, w_color, w_depth, w_dist, *, order=None, 
     depth_near, depth_far), the operator's backward in the calling thread with the parameter gradients landing in `opt.bucket`,
     opt.step(), then `stats.add(pkg['radius'], means2D.grad)` when a DensificationStats is given, and every `densify_interval`
     iterations densify.densify_and_prune(opt, stats, densify_cfg, generator).
+
+    exposures (render.enable_exposure): a list parallel to `frames` of None or (ExposureOptimizer, base or None).  Such a frame
+    is scored at optimizer.value(base) and the optimiser is stepped with the loss's dL/dexposure once it has been visited more
+    than `exposure_after` times in this call: the count per optimiser OBJECT plays the reference's `mapping_times` -- per frame
+    in the frontend (threshold 10), per local map in the backend, where the frames share one optimiser (threshold 120).  Below
+    the threshold neither the step nor the schedule advances.  With exposures=None nothing changes.
 
     Returns (last render package, last loss as a 0-dim device tensor, iterations run).  Nothing here reads from the device
     beyond the operator's own one read per forward (and densify_and_prune's one per call)."""
@@ -150,22 +156,38 @@ def map_frames(opt, frames, num_iters, w_color, w_depth, w_dist, *, order=None, 
     require(len(order) >= num_iters, "order must give a frame index for every iteration")
     if densify_interval:
         require(stats is not None and densify_cfg is not None, "densify_interval needs stats and densify_cfg")
+    if exposures is not None:
+        from .exposure import ExposureOptimizer
+        require(len(exposures) == len(frames), "exposures must be parallel to frames")
+        for e in exposures:
+            require(e is None or (isinstance(e, (tuple, list)) and len(e) == 2 and isinstance(e[0], ExposureOptimizer)),
+                    "an entry of exposures must be None or (ExposureOptimizer, base or None)")
+    visits = {}  # id(optimizer) -> mapping_times
     pkg = loss = None
     done = 0
     with torch.autograd.set_multithreading_enabled(False):
         for it in range(num_iters):
             settings, gt_color, gt_depth = frames[order[it]]
+            ex = exposures[order[it]] if exposures is not None else None
             leaves = opt.render_leaves()
             m2 = torch.zeros_like(leaves["means3D"], requires_grad=True)
             pkg = _render.render(settings, leaves["means3D"], m2, leaves["opacities"], colors_precomp=leaves["colors"],
                                  scales=leaves["scales"], rotations=leaves["rotations"])
-            loss, g_color, g_allmap = _loss.mapping_loss_and_grads(pkg["render_color"], pkg["allmap"], gt_color, gt_depth,
-                                                                   w_color, w_depth, w_dist, **loss_kwargs)
+            if ex is None:
+                loss, g_color, g_allmap = _loss.mapping_loss_and_grads(pkg["render_color"], pkg["allmap"], gt_color, gt_depth,
+                                                                       w_color, w_depth, w_dist, **loss_kwargs)
+            else:
+                loss, g_color, g_allmap, g_ex = _loss.mapping_loss_and_grads(
+                    pkg["render_color"], pkg["allmap"], gt_color, gt_depth, w_color, w_depth, w_dist, exposure=ex[0].value(ex[1]),
+                    **loss_kwargs)
             bucket = opt.bucket
             with _rasterizer.grad_sink(bucket.views):
                 torch.autograd.backward([pkg["render_color"], pkg["allmap"]], [g_color, g_allmap])
             bucket.pack({n: t.grad for n, t in leaves.items()})  # no copy for what the backward wrote in place
             opt.step(leaves=leaves)
+            if ex is not None:
+                visits[id(ex[0])] = visits.get(id(ex[0]), 0) + 1
+                ex[0].step(g_ex, ex[1], apply=visits[id(ex[0])] > exposure_after)
             done += 1
             if stats is not None:
                 stats.add(pkg["radius"], m2.grad)

@@ -178,7 +178,9 @@ def track(settings, opt, means3D, opacities, colors, scales, rotations, gt_color
     makes the iterations launched after the reference's `break` no-ops, so the pose is the one the reference ends with.
 
     settings: the identity-view raster settings of tracking.render_tracking; loss_kw: silmask_th, use_weight_norm, eps,
-    depth_near, depth_far of loss.tracking_loss_and_grads.  Returns (last render package, last loss tensor, opt); the number of
+    depth_near, depth_far of loss.tracking_loss_and_grads, and its two switches: exposure=E (render.enable_exposure: the frame's
+    effective exposure, a float32 device tensor of two elements, held constant as the reference detaches it) and
+    ignore_outliers=True (loss.ignore_outliners: the median test of slam/Loss.py:37-40); neither adds a host read.  Returns (last render package, last loss tensor, opt); the number of
     Adam steps taken is opt.state()["steps"].
 
     Departure from the reference: when the loop overruns the latch, the returned package was rendered AT the final pose; the
