@@ -3,7 +3,8 @@ growth / pruning library, which also holds the camera pose optimiser, the evalua
 reconstruction metrics (C ABI in include/gs2d_map.h, include/gs2d_pose.h, include/gs2d_eval.h, include/gs2d_tsdf.h and
 include/gs2d_recon.h, sources in csrc_map/), the mesh library: the triangle-mesh depth renderer with Depth L1 and clean_mesh
 (C ABI in include/gs2d_mesh.h, sources in csrc_mesh/), and the loss library: the fused SLAM loss with exposure and the tracking
-outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources in csrc_loss/).
+outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources in csrc_loss/), and the volume library: the
+block-hashed TSDF volume (C ABI in include/gs2d_vol.h, sources in csrc_vol/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -45,6 +46,13 @@ CSRC_LOSS = os.path.join(_HERE, "csrc_loss")
 LOSS_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_loss_hip.so")
 LOSS_SOURCES = ["gs2d_loss_ex.hip"]
 LOSS_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_loss.h")]
+
+# The block-hashed TSDF volume is a fifth library: tests pin the map library's symbols, headers and hash, so it restates the
+# integration rule and the tetrahedron table of csrc_map/gs2d_tsdf.hip.  It includes ../csrc/gs2d_scan.h and gs2d_common.h only.
+CSRC_VOL = os.path.join(_HERE, "csrc_vol")
+VOL_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_vol_hip.so")
+VOL_SOURCES = ["gs2d_vol.hip"]
+VOL_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_vol.h")]
 
 
 def _hash(directory, headers):
@@ -150,11 +158,30 @@ def build_loss(force=False, verbose=False):
     return _compile(LOSS_LIB_PATH, [os.path.join(CSRC_LOSS, f) for f in LOSS_SOURCES], "GS2D_LOSS_SOURCE_HASH", loss_source_hash(), verbose)
 
 
+def vol_source_hash():
+    """source_hash() of the volume library: every file under csrc_vol/ plus VOL_HEADERS (gs2d_vol_build_info reports it)."""
+    return _hash(CSRC_VOL, VOL_HEADERS)
+
+
+def _vol_stale():
+    """Like the map library, the volume library includes ../csrc/gs2d_scan.h and gs2d_common.h."""
+    deps = [os.path.join(CSRC_VOL, f) for f in os.listdir(CSRC_VOL)] + VOL_HEADERS + [os.path.join(CSRC, "gs2d_scan.h"),
+                                                                                      os.path.join(CSRC, "gs2d_common.h")]
+    return _is_stale(VOL_LIB_PATH, vol_source_hash(), deps)
+
+
+def build_vol(force=False, verbose=False):
+    if not force and not _vol_stale():
+        return VOL_LIB_PATH
+    return _compile(VOL_LIB_PATH, [os.path.join(CSRC_VOL, f) for f in VOL_SOURCES], "GS2D_VOL_SOURCE_HASH", vol_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the four libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the five libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
+    build_vol(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -167,3 +194,4 @@ if __name__ == "__main__":
     print(MAP_LIB_PATH)
     print(MESH_LIB_PATH)
     print(LOSS_LIB_PATH)
+    print(VOL_LIB_PATH)

@@ -116,7 +116,8 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     existing operator; its metrics go to row k of one [K, EVAL_OUT_DOUBLES] device tensor, which is read once at the end.
     Returns a dict: per-frame float64 arrays `psnr`, `ms_ssim`, `depth_rmse`, `depth_l1`, their means `mean_psnr`, ...,
     `per_frame` (the whole [K, EVAL_OUT_DOUBLES] array) and, when both pose lists are given, `ate_rmse`.
-    tsdf: a tsdf.TSDFVolume.  Every mesh_interval-th frame's render -- the one made for the metrics -- is then fused into it with
+    tsdf: a tsdf.TSDFVolume or a tsdf_blocks.BlockTSDFVolume (which adds its allocation launch and, with its default grow=True,
+    one 8-byte host read per fused frame).  Every mesh_interval-th frame's render -- the one made for the metrics -- is then fused into it with
     integrate_render (eval.py:378-399), one more launch per such frame and no host read, with the same depth normalisation as
     the metrics.  mesh_intrinsics: (fx, fy, cx, cy) or a 3x3, host values (the raster settings do not carry the principal
     point on the host).  mesh_extrinsics: one float32 [4,4] world-to-camera matrix on the device per frame; None takes the
