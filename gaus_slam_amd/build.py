@@ -3,8 +3,9 @@ growth / pruning library, which also holds the camera pose optimiser, the evalua
 reconstruction metrics (C ABI in include/gs2d_map.h, include/gs2d_pose.h, include/gs2d_eval.h, include/gs2d_tsdf.h and
 include/gs2d_recon.h, sources in csrc_map/), the mesh library: the triangle-mesh depth renderer with Depth L1 and clean_mesh
 (C ABI in include/gs2d_mesh.h, sources in csrc_mesh/), and the loss library: the fused SLAM loss with exposure and the tracking
-outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources in csrc_loss/), and the volume library: the
-block-hashed TSDF volume (C ABI in include/gs2d_vol.h, sources in csrc_vol/).
+outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources in csrc_loss/), the volume library: the
+block-hashed TSDF volume (C ABI in include/gs2d_vol.h, sources in csrc_vol/), and the covisibility library: the keyframe bank
+(C ABI in include/gs2d_covis.h, sources in csrc_covis/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -53,6 +54,13 @@ CSRC_VOL = os.path.join(_HERE, "csrc_vol")
 VOL_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_vol_hip.so")
 VOL_SOURCES = ["gs2d_vol.hip"]
 VOL_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_vol.h")]
+
+# The keyframe bank is a sixth library: every older library's exported symbols are pinned by its host test.  It includes nothing
+# of csrc/.
+CSRC_COVIS = os.path.join(_HERE, "csrc_covis")
+COVIS_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_covis_hip.so")
+COVIS_SOURCES = ["gs2d_covis.hip"]
+COVIS_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_covis.h")]
 
 
 def _hash(directory, headers):
@@ -176,12 +184,29 @@ def build_vol(force=False, verbose=False):
     return _compile(VOL_LIB_PATH, [os.path.join(CSRC_VOL, f) for f in VOL_SOURCES], "GS2D_VOL_SOURCE_HASH", vol_source_hash(), verbose)
 
 
+def covis_source_hash():
+    """source_hash() of the covisibility library: every file under csrc_covis/ plus COVIS_HEADERS (gs2d_covis_build_info reports it)."""
+    return _hash(CSRC_COVIS, COVIS_HEADERS)
+
+
+def _covis_stale():
+    deps = [os.path.join(CSRC_COVIS, f) for f in os.listdir(CSRC_COVIS)] + COVIS_HEADERS
+    return _is_stale(COVIS_LIB_PATH, covis_source_hash(), deps)
+
+
+def build_covis(force=False, verbose=False):
+    if not force and not _covis_stale():
+        return COVIS_LIB_PATH
+    return _compile(COVIS_LIB_PATH, [os.path.join(CSRC_COVIS, f) for f in COVIS_SOURCES], "GS2D_COVIS_SOURCE_HASH", covis_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the five libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the six libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
     build_vol(force, verbose)
+    build_covis(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -195,3 +220,4 @@ if __name__ == "__main__":
     print(MESH_LIB_PATH)
     print(LOSS_LIB_PATH)
     print(VOL_LIB_PATH)
+    print(COVIS_LIB_PATH)
