@@ -5,7 +5,8 @@ include/gs2d_recon.h, sources in csrc_map/), the mesh library: the triangle-mesh
 (C ABI in include/gs2d_mesh.h, sources in csrc_mesh/), and the loss library: the fused SLAM loss with exposure and the tracking
 outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources in csrc_loss/), the volume library: the
 block-hashed TSDF volume (C ABI in include/gs2d_vol.h, sources in csrc_vol/), and the covisibility library: the keyframe bank
-(C ABI in include/gs2d_covis.h, sources in csrc_covis/).
+(C ABI in include/gs2d_covis.h, sources in csrc_covis/), and the LPIPS library: the AlexNet trunk on the f32 MFMA and the metric's
+tail (C ABI in include/gs2d_lpips.h, sources in csrc_lpips/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -61,6 +62,12 @@ CSRC_COVIS = os.path.join(_HERE, "csrc_covis")
 COVIS_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_covis_hip.so")
 COVIS_SOURCES = ["gs2d_covis.hip"]
 COVIS_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_covis.h")]
+
+# LPIPS is a seventh library, for the same reason.  It includes nothing of csrc/.
+CSRC_LPIPS = os.path.join(_HERE, "csrc_lpips")
+LPIPS_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_lpips_hip.so")
+LPIPS_SOURCES = ["gs2d_lpips.hip"]
+LPIPS_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_lpips.h")]
 
 
 def _hash(directory, headers):
@@ -200,13 +207,30 @@ def build_covis(force=False, verbose=False):
     return _compile(COVIS_LIB_PATH, [os.path.join(CSRC_COVIS, f) for f in COVIS_SOURCES], "GS2D_COVIS_SOURCE_HASH", covis_source_hash(), verbose)
 
 
+def lpips_source_hash():
+    """source_hash() of the LPIPS library: every file under csrc_lpips/ plus LPIPS_HEADERS (gs2d_lpips_build_info reports it)."""
+    return _hash(CSRC_LPIPS, LPIPS_HEADERS)
+
+
+def _lpips_stale():
+    deps = [os.path.join(CSRC_LPIPS, f) for f in os.listdir(CSRC_LPIPS)] + LPIPS_HEADERS
+    return _is_stale(LPIPS_LIB_PATH, lpips_source_hash(), deps)
+
+
+def build_lpips(force=False, verbose=False):
+    if not force and not _lpips_stale():
+        return LPIPS_LIB_PATH
+    return _compile(LPIPS_LIB_PATH, [os.path.join(CSRC_LPIPS, f) for f in LPIPS_SOURCES], "GS2D_LPIPS_SOURCE_HASH", lpips_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the six libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the seven libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
     build_vol(force, verbose)
     build_covis(force, verbose)
+    build_lpips(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -221,3 +245,4 @@ if __name__ == "__main__":
     print(LOSS_LIB_PATH)
     print(VOL_LIB_PATH)
     print(COVIS_LIB_PATH)
+    print(LPIPS_LIB_PATH)

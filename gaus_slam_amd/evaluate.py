@@ -11,9 +11,13 @@ row per frame in a device tensor and reads the host once at the end.
     res = evaluate_map(params, frames, est_w2cs=est, gt_w2cs=gt)                  # dict: psnr, ms_ssim, depth_rmse, depth_l1, ate_rmse
 
     res = evaluate_map(params, frames, tsdf=vol, mesh_intrinsics=K)                # also fuses the renders into a tsdf.TSDFVolume
+    res = evaluate_map(params, frames, lpips=lpips.LPIPS.from_files(alex, lin))    # also lpips, mean_lpips (eval.py:409-410)
 
-Not covered: LPIPS (it needs the AlexNet weights of the `lpips` package), the mesh metrics of utils/eval_mesh.py, and saving
-the rendered images.  The TSDF mesh itself is gaus_slam_amd/tsdf.py.
+LPIPS is gaus_slam_amd/lpips.py (include/gs2d_lpips.h): a model built from the two weight files a user of the reference has on
+disk; no weights ship here and none are fetched.  The published network's weights were never available to this project, so the
+agreement with torchmetrics on them is unverified: what is verified is the arithmetic on random weights and the loader's key
+mapping.  Not covered: the mesh metrics of utils/eval_mesh.py, and saving the rendered images.  The TSDF mesh itself is
+gaus_slam_amd/tsdf.py.
 
 No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError."""
 import numpy as np
@@ -22,6 +26,7 @@ import torch
 from . import _map_lib
 from ._map_lib import (EVAL_DEPTH_L1, EVAL_DEPTH_RMSE, EVAL_LEVEL, EVAL_MS_SSIM, EVAL_MS_SSIM_C, EVAL_MSE, EVAL_N_VALID,  # noqa: F401
                        EVAL_OUT_DOUBLES, EVAL_PSNR)
+from ._lpips_lib import OUT_DOUBLES as LPIPS_OUT_DOUBLES, VALUE as LPIPS_VALUE
 from ._check import check_device, check_frame, check_tensor, check_vector, require
 
 MIN_SIDE = 160  # pytorch_msssim's assertion: the smaller side must exceed (11 - 1) * 2^4
@@ -109,7 +114,7 @@ def _umeyama_rigid(x, y):
 
 
 def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2,
-                 clamp_color=False, tsdf=None, mesh_interval=1, mesh_extrinsics=None, mesh_intrinsics=None):
+                 clamp_color=False, tsdf=None, mesh_interval=1, mesh_extrinsics=None, mesh_intrinsics=None, lpips=None):
     """eval_final's loop over the frames.  params: the activated leaves render.render takes, a dict with means3D, opacities,
     scales, rotations and colors (or colors_precomp, or shs).  frames: a sequence of (settings, gt_color, gt_depth), the raster
     settings of each view (at its estimated pose) and its RGB-D frame.  Every view is rendered under torch.no_grad() with the
@@ -122,7 +127,11 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     the metrics.  mesh_intrinsics: (fx, fy, cx, cy) or a 3x3, host values (the raster settings do not carry the principal
     point on the host).  mesh_extrinsics: one float32 [4,4] world-to-camera matrix on the device per frame; None takes the
     frame's own view matrix.  The reference passes est_w2c @ first_w2c @ P with P the ScanNet++ axis swap: the caller composes
-    that.  With tsdf=None nothing changes: the same launches and the same bits."""
+    that.  With tsdf=None nothing changes: the same launches and the same bits.
+    lpips: an lpips.LPIPS model.  Every frame's render then also goes through lpips.frame (fourteen more launches per frame, no
+    host read) into row k of a second device tensor, read at the end with the first: the result gains `lpips` (per frame),
+    `mean_lpips` and `lpips_per_frame` (the whole [K, LPIPS_OUT_DOUBLES] array).  With lpips=None nothing changes: the same
+    launches and the same bits."""
     from . import render as _render
     require(len(frames) >= 1, "frames is empty")
     if tsdf is not None:
@@ -138,6 +147,8 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
     rows = torch.empty((len(frames), EVAL_OUT_DOUBLES), dtype=torch.float64, device=dev)
     ws = None
+    lpips_rows = None if lpips is None else torch.empty((len(frames), LPIPS_OUT_DOUBLES), dtype=torch.float64, device=dev)
+    lpips_ws = None
     with torch.no_grad():
         means2D = torch.zeros_like(p["means3D"])
         for k, (settings, gt_color, gt_depth) in enumerate(frames):
@@ -148,6 +159,10 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
                 ws = workspace(W, H, dev)
             frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, use_weight_norm=use_weight_norm, eps=eps,
                           depth_near=depth_near, depth_far=depth_far, clamp_color=clamp_color, out=rows[k], ws=ws)
+            if lpips is not None:
+                if lpips_ws is None or lpips_ws.numel() < lpips.ws_bytes(W, H):
+                    lpips_ws = lpips.workspace(W, H)
+                lpips.frame(pkg["render_color"], gt_color, gt_depth, out=lpips_rows[k], ws=lpips_ws)
             if tsdf is not None and k % int(mesh_interval) == 0:
                 w2c = mesh_extrinsics[k] if mesh_extrinsics is not None else settings.viewmatrix.reshape(4, 4).t().contiguous()
                 tsdf.integrate_render(pkg["render_color"], pkg["allmap"], mesh_intrinsics, w2c, use_weight_norm=use_weight_norm,
@@ -157,6 +172,10 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     for name, col in (("psnr", EVAL_PSNR), ("ms_ssim", EVAL_MS_SSIM), ("depth_rmse", EVAL_DEPTH_RMSE), ("depth_l1", EVAL_DEPTH_L1)):
         res[name] = host[:, col].copy()
         res["mean_" + name] = float(host[:, col].mean())
+    if lpips is not None:
+        res["lpips_per_frame"] = lpips_rows.cpu().numpy()
+        res["lpips"] = res["lpips_per_frame"][:, LPIPS_VALUE].copy()
+        res["mean_lpips"] = float(res["lpips"].mean())
     if est_w2cs is not None:
         res["ate_rmse"] = ate_rmse(est_w2cs, gt_w2cs)
     return res
