@@ -6,7 +6,8 @@ include/gs2d_recon.h, sources in csrc_map/), the mesh library: the triangle-mesh
 outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources in csrc_loss/), the volume library: the
 block-hashed TSDF volume (C ABI in include/gs2d_vol.h, sources in csrc_vol/), and the covisibility library: the keyframe bank
 (C ABI in include/gs2d_covis.h, sources in csrc_covis/), and the LPIPS library: the AlexNet trunk on the f32 MFMA and the metric's
-tail (C ABI in include/gs2d_lpips.h, sources in csrc_lpips/).
+tail (C ABI in include/gs2d_lpips.h, sources in csrc_lpips/), and the frontend library: sensor-frame ingest, the frame-closing
+decision and batched camera set-up (C ABI in include/gs2d_front.h, sources in csrc_front/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -68,6 +69,12 @@ CSRC_LPIPS = os.path.join(_HERE, "csrc_lpips")
 LPIPS_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_lpips_hip.so")
 LPIPS_SOURCES = ["gs2d_lpips.hip"]
 LPIPS_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_lpips.h")]
+
+# The frontend steps are an eighth library, for the same reason.  It includes nothing of csrc/.
+CSRC_FRONT = os.path.join(_HERE, "csrc_front")
+FRONT_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_front_hip.so")
+FRONT_SOURCES = ["gs2d_front.hip"]
+FRONT_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_front.h")]
 
 
 def _hash(directory, headers):
@@ -223,14 +230,31 @@ def build_lpips(force=False, verbose=False):
     return _compile(LPIPS_LIB_PATH, [os.path.join(CSRC_LPIPS, f) for f in LPIPS_SOURCES], "GS2D_LPIPS_SOURCE_HASH", lpips_source_hash(), verbose)
 
 
+def front_source_hash():
+    """source_hash() of the frontend library: every file under csrc_front/ plus FRONT_HEADERS (gs2d_front_build_info reports it)."""
+    return _hash(CSRC_FRONT, FRONT_HEADERS)
+
+
+def _front_stale():
+    deps = [os.path.join(CSRC_FRONT, f) for f in os.listdir(CSRC_FRONT)] + FRONT_HEADERS
+    return _is_stale(FRONT_LIB_PATH, front_source_hash(), deps)
+
+
+def build_front(force=False, verbose=False):
+    if not force and not _front_stale():
+        return FRONT_LIB_PATH
+    return _compile(FRONT_LIB_PATH, [os.path.join(CSRC_FRONT, f) for f in FRONT_SOURCES], "GS2D_FRONT_SOURCE_HASH", front_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the seven libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the eight libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
     build_vol(force, verbose)
     build_covis(force, verbose)
     build_lpips(force, verbose)
+    build_front(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -246,3 +270,4 @@ if __name__ == "__main__":
     print(VOL_LIB_PATH)
     print(COVIS_LIB_PATH)
     print(LPIPS_LIB_PATH)
+    print(FRONT_LIB_PATH)
