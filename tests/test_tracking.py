@@ -8,10 +8,11 @@ import torch
 from tests import util
 
 
-def _world_scene(P, W, H, seed):
-    """Camera-space scene + a random w2c; Gaussians moved to the world frame so that w2c brings them back."""
+def _world_scene(P, W, H, seed, sc=None):
+    """Camera-space scene + a random w2c; Gaussians moved to the world frame so that w2c brings them back.
+    sc: a camera-space scene (identity view) to use instead of make_scene's."""
     from gaus_slam_amd.scene_synth import random_w2c
-    sc = util.make_scene(P, W, H, seed=seed, regime="tracking")
+    sc = util.make_scene(P, W, H, seed=seed, regime="tracking") if sc is None else sc
     w2c = random_w2c(np.random.default_rng(seed + 100), max_rot_deg=25.0, max_trans=0.5).double()
     c2w = torch.inverse(w2c)
     means_w = (sc["means3D"].double() @ c2w[:3, :3].T + c2w[:3, 3]).float()

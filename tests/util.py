@@ -65,6 +65,123 @@ def make_planar_scene(P, W, H, seed=0, regime="tracking", plane="wall", dist=3.0
     return out
 
 
+def make_camera_scene(P, W, H, intr, w2c, seed=0, cull_frac=0.03, scale_lo=0.7, scale_hi=4.0, max_tilt_deg=75.0):
+    """make_scene's recipe for an arbitrary pinhole intr = (fx, fy, cx, cy) and rigid w2c [4,4]: u, v uniform over
+    [-0.05, 1.05] x (W, H), z in [0.5, 6], means in the camera frame at ((u - cx) / fx z, (v - cy) / fy z, z), the footprint in
+    pixels scaled by sqrt(fx fy), normals / spins / opacities / colours as make_scene, cull_frac of the splats behind the near
+    plane or far off-screen; then everything moved into the world frame of w2c.  The camera is scene_synth.setup_camera's, so
+    the oracle and the library are fed identical bits.  Returns make_scene's dict."""
+    import math
+    from gaus_slam_amd.scene_synth import _rotmat_to_quat_wxyz, setup_camera
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = (float(a) for a in intr)
+    K = torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=torch.float32)
+    u = rng.uniform(-0.05, 1.05, P) * W
+    v = rng.uniform(-0.05, 1.05, P) * H
+    z = rng.uniform(0.5, 6.0, P)
+    ncull = int(round(cull_frac * P))
+    if ncull > 0:
+        half = ncull // 2
+        z[:half] = rng.uniform(-1.0, 0.19, half)                 # behind the near plane
+        u[half:ncull] = rng.uniform(1.5, 3.0, ncull - half) * W  # far off-screen
+    mean_cam = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1)
+    s = np.exp(rng.uniform(math.log(scale_lo), math.log(scale_hi), (P, 2)))
+    scales = (np.abs(z)[:, None] + 1e-3) / math.sqrt(fx * fy) * s
+    to_cam = -mean_cam / (np.linalg.norm(mean_cam, axis=1, keepdims=True) + 1e-12)
+    helper = np.where(np.abs(to_cam[:, :1]) < 0.9, np.array([[1.0, 0, 0]]), np.array([[0, 1.0, 0]]))
+    t1 = np.cross(to_cam, helper); t1 /= np.linalg.norm(t1, axis=1, keepdims=True)
+    t2 = np.cross(to_cam, t1)
+    tilt = np.radians(rng.uniform(0, max_tilt_deg, P))
+    az = rng.uniform(0, 2 * math.pi, P)
+    n = np.cos(tilt)[:, None] * to_cam + np.sin(tilt)[:, None] * (np.cos(az)[:, None] * t1 + np.sin(az)[:, None] * t2)
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    h2 = np.where(np.abs(n[:, :1]) < 0.9, np.array([[1.0, 0, 0]]), np.array([[0, 1.0, 0]]))
+    a1 = np.cross(n, h2); a1 /= np.linalg.norm(a1, axis=1, keepdims=True)
+    a2 = np.cross(n, a1)
+    spin = rng.uniform(0, 2 * math.pi, P)
+    e1 = np.cos(spin)[:, None] * a1 + np.sin(spin)[:, None] * a2
+    Rm = np.stack([e1, np.cross(n, e1), n], 2)  # columns: tangent u, tangent v, normal
+    opac = np.clip(1.0 / (1.0 + np.exp(-rng.normal(0, 1.5, P))), 0.02, 0.99)
+    colors = rng.uniform(0, 1, (P, 3))
+    w2c = torch.as_tensor(np.asarray(w2c, np.float64))
+    c2w = np.linalg.inv(w2c.numpy())
+    means = mean_cam @ c2w[:3, :3].T + c2w[:3, 3]
+    quat = _rotmat_to_quat_wxyz(np.einsum("ij,njk->nik", c2w[:3, :3], Rm))
+    cam = setup_camera(W, H, K, w2c.float())
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).float()
+    return dict(means3D=t(means), scales=t(scales), rotations=t(quat), opacities=t(opac[:, None]), colors=t(colors), cam=cam)
+
+
+def rebuilt_size(W, H, tanfovx, tanfovy):
+    """The image size the backward works with (backward.cu:641-642 behind rasterizer_impl.cu:396-397; gs2d_api.hip and both
+    oracles follow it): focal = size / (2 tan), rebuilt = (int)(focal * tan * 2), all in float32.  For some focal lengths the
+    product rounds just below the integer and the result is size - 1 ("The backward's image size")."""
+    f = np.float32
+    tx, ty = f(tanfovx), f(tanfovy)
+    focal_x, focal_y = f(W) / (f(2.0) * tx), f(H) / (f(2.0) * ty)
+    return int(f(focal_x * tx) * f(2.0)), int(f(focal_y * ty) * f(2.0))
+
+
+def _tanfov32(n, focal):
+    """setup_camera's tan(fov / 2), by its own expression (torch evaluates int / tensor as reciprocal x int, in float32)."""
+    return float(n / (2 * torch.tensor(focal, dtype=torch.float32)))
+
+
+def truncating_focals(W, H):
+    """The first fx >= 0.8 W and fy >= 0.85 W, in steps of 1/16 px (exact in float32), whose rebuilt size is W - 1 resp. H - 1."""
+    def search(n, start):
+        for k in range(100000):
+            focal = float(np.float32(np.floor(start * 16.0) / 16.0 + k / 16.0))
+            t = _tanfov32(n, focal)
+            if rebuilt_size(n, n, t, t)[0] == n - 1:
+                return focal
+        raise AssertionError("no truncating focal length found")
+    return search(W, 0.8 * W), search(H, 0.85 * W)
+
+
+def _rot(axis, deg):
+    a = np.asarray(axis, np.float64); a = a / np.linalg.norm(a)
+    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    r = np.radians(deg)
+    return np.eye(3) + np.sin(r) * Kx + (1 - np.cos(r)) * Kx @ Kx
+
+
+def _rigid(R, t):
+    M = np.eye(4)
+    M[:3, :3], M[:3, 3] = R, t
+    return M
+
+
+_X, _Y, _Z = (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)
+_centre = lambda W, H: ((W - 1) / 2.0, (H - 1) / 2.0)
+REAL_CAMERAS = {
+    # name: (intr(W, H) -> (fx, fy, cx, cy), w2c [4,4] float64)
+    "tum_fr1": (lambda W, H: (517.3 * W / 640, 516.5 * H / 480, 318.6 * W / 640, 255.3 * H / 480),
+                _rigid(_rot((1.0, 2.0, 0.5), 20.0), (0.2, -0.1, 0.3))),
+    # (fx = 0.9 W would rebuild 95 at 96 wide)
+    "anisotropic": (lambda W, H: (0.92 * W, 0.6 * W) + _centre(W, H), _rigid(_rot((0.3, 1.0, 0.2), 35.0), (-0.3, 0.2, 0.1))),
+    "off_centre": (lambda W, H: (0.8 * W, 0.8 * W, 0.25 * W, 0.7 * H), _rigid(_rot(_Y, 110.0), (1.0, 0.0, 2.0))),
+    "rolled": (lambda W, H: (0.82 * W, 0.82 * W) + _centre(W, H), _rigid(_rot(_Z, 90.0) @ _rot(_X, 15.0), (0.1, 0.2, -0.2))),
+    "flipped": (lambda W, H: (0.82 * W, 0.82 * W) + _centre(W, H), _rigid(_rot(_Z, 180.0) @ _rot(_Y, 170.0), (-0.2, 0.1, 0.4))),
+    "truncating": (lambda W, H: truncating_focals(W, H) + _centre(W, H), _rigid(_rot((1.0, -1.0, 0.3), 12.0), (0.15, -0.25, 0.2))),
+    "pp_outside": (lambda W, H: (0.8 * W, 0.8 * W, -0.2 * W, (H - 1) / 2.0), _rigid(_rot((0.2, 1.0, -0.1), 8.0), (0.3, 0.1, -0.1))),
+}
+"""Cameras no make_scene test has: fx != fy, an off-centre principal point (inside and outside the image), views rolled a
+quarter and a half turn or facing backwards, a camera centre 2.2 m from the origin, and one whose focal lengths make the backward
+rebuild the image size as (W - 1, H - 1) (rebuilt_size).  Every other camera rebuilds (W, H): tests assert either on the host."""
+
+
+def real_camera_scene(name, P, W, H, seed=0, identity_view=False, **kw):
+    """make_camera_scene under REAL_CAMERAS[name]; the condition on the rebuilt size is asserted here for every caller.
+    identity_view: the camera's intrinsics with w2c = I (the tracking regime)."""
+    intr, w2c = REAL_CAMERAS[name]
+    sc = make_camera_scene(P, W, H, intr(W, H), np.eye(4) if identity_view else w2c, seed=seed, **kw)
+    cam = sc["cam"]
+    want = (W - 1, H - 1) if name == "truncating" else (W, H)
+    assert rebuilt_size(W, H, cam.tanfovx, cam.tanfovy) == want, (name, W, H, rebuilt_size(W, H, cam.tanfovx, cam.tanfovy))
+    return sc
+
+
 def oracle_forward(orc, sc, use_sa=True, bg=(0.0, 0.0, 0.0), shs=None, sh_degree=0, transMat_precomp=None,
                    scale_modifier=1.0):
     cam = sc["cam"]
