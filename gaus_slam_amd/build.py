@@ -7,7 +7,8 @@ outlier test, and the exposure optimiser (C ABI in include/gs2d_loss.h, sources 
 block-hashed TSDF volume (C ABI in include/gs2d_vol.h, sources in csrc_vol/), and the covisibility library: the keyframe bank
 (C ABI in include/gs2d_covis.h, sources in csrc_covis/), and the LPIPS library: the AlexNet trunk on the f32 MFMA and the metric's
 tail (C ABI in include/gs2d_lpips.h, sources in csrc_lpips/), and the frontend library: sensor-frame ingest, the frame-closing
-decision and batched camera set-up (C ABI in include/gs2d_front.h, sources in csrc_front/).
+decision and batched camera set-up (C ABI in include/gs2d_front.h, sources in csrc_front/), and the ingest library: the sensor-frame
+ingest with separate colour and depth sizes and colour undistortion (C ABI in include/gs2d_ingest.h, sources in csrc_ingest/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -75,6 +76,13 @@ CSRC_FRONT = os.path.join(_HERE, "csrc_front")
 FRONT_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_front_hip.so")
 FRONT_SOURCES = ["gs2d_front.hip"]
 FRONT_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_front.h")]
+
+# The extended ingest is a ninth library: the frontend library's symbols are pinned by its host test too.  It includes nothing of
+# csrc/ and restates the resize rule of csrc_front/gs2d_front.hip.
+CSRC_INGEST = os.path.join(_HERE, "csrc_ingest")
+INGEST_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_ingest_hip.so")
+INGEST_SOURCES = ["gs2d_ingest.hip"]
+INGEST_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_ingest.h")]
 
 
 def _hash(directory, headers):
@@ -246,8 +254,24 @@ def build_front(force=False, verbose=False):
     return _compile(FRONT_LIB_PATH, [os.path.join(CSRC_FRONT, f) for f in FRONT_SOURCES], "GS2D_FRONT_SOURCE_HASH", front_source_hash(), verbose)
 
 
+def ingest_source_hash():
+    """source_hash() of the ingest library: every file under csrc_ingest/ plus INGEST_HEADERS (gs2d_ingest_build_info reports it)."""
+    return _hash(CSRC_INGEST, INGEST_HEADERS)
+
+
+def _ingest_stale():
+    deps = [os.path.join(CSRC_INGEST, f) for f in os.listdir(CSRC_INGEST)] + INGEST_HEADERS
+    return _is_stale(INGEST_LIB_PATH, ingest_source_hash(), deps)
+
+
+def build_ingest(force=False, verbose=False):
+    if not force and not _ingest_stale():
+        return INGEST_LIB_PATH
+    return _compile(INGEST_LIB_PATH, [os.path.join(CSRC_INGEST, f) for f in INGEST_SOURCES], "GS2D_INGEST_SOURCE_HASH", ingest_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the eight libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the nine libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
@@ -255,6 +279,7 @@ def build(force=False, verbose=False):
     build_covis(force, verbose)
     build_lpips(force, verbose)
     build_front(force, verbose)
+    build_ingest(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -271,3 +296,4 @@ if __name__ == "__main__":
     print(COVIS_LIB_PATH)
     print(LPIPS_LIB_PATH)
     print(FRONT_LIB_PATH)
+    print(INGEST_LIB_PATH)

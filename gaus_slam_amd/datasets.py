@@ -1,0 +1,245 @@
+"""Readers of recorded RGB-D sequences, as sequences for slam.run_slam: plain Python on the CPU, written from the on-disk layouts
+of the reference's datasets (datasets/gradslam_datasets/{replica,tum,scannet}.py), not from its loaders.
+
+    seq = ReplicaSequence(basedir, "kitchen", camera)        # camera: the camera_params mapping of a camera.yaml
+    seq = open_sequence(config["data"])                      # from a reference config's `data` section
+    for color_u8, depth, gt_c2w in seq: ...                  # uint8 [Hc,Wc,3], uint16 [Hd,Wd], float32 [4,4] camera-to-world
+    seq.intrinsics, seq.png_depth_scale, seq.size            # (fx, fy, cx, cy) at the colour size, units per metre, (Wc, Hc)
+    seq.depth_size, seq.distortion                           # (Wd, Hd); None or (k1, k2, p1, p2, k3)
+
+Nothing is resized, undistorted or scaled here: that is one launch per frame on the device (frontend_ops.ingest / ingest_ex),
+which run_slam chooses by depth_size and distortion.  Images are decoded with Pillow and camera files with PyYAML, both imported
+where they are first needed; a missing one raises an error that names it.  File names are ordered naturally (frame_2 before
+frame_10).  start / end / stride select frames[start:end:stride] as the reference does, end == -1 meaning all, with its refusals:
+ValueError for start < 0, for an end that is neither -1 nor above start, and for colour and depth lists of different lengths.
+`crop_edge` of a camera file is read and ignored: the reference never applies it.
+
+Departures: the TUM pose list is read without its comment lines and nothing else is skipped (the reference also drops the first
+line, which is a comment in every published sequence); ScanNetSequence(ignore_bad=True) drops the frames of the selected range
+whose pose is not finite (the reference accepts the flag and leaves such frames in)."""
+import glob
+import math
+import os
+import re
+
+import numpy as np
+import torch
+
+KNOWN = ("replica", "tum", "scannet")
+MAX_DT = 0.08  # seconds between a colour stamp and the depth / pose stamp associated with it (TUM)
+FRAME_RATE = 32  # successive TUM frames are more than 1 / FRAME_RATE seconds apart
+
+
+def _need(module, package):
+    try:
+        return __import__(module, fromlist=["_"])
+    except ImportError as e:
+        raise RuntimeError(f"gaus_slam_amd.datasets needs the {package} package, which is not installed ({e})") from e
+
+
+def natural_key(path):
+    """Sort key of a file name: digit runs compare as numbers."""
+    return [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", os.path.basename(path))]
+
+
+def natural_glob(pattern):
+    return sorted(glob.glob(pattern), key=natural_key)
+
+
+def quaternion_pose(vec):
+    """tx ty tz qx qy qz qw -> float64 [4,4] camera-to-world; the quaternion is normalised first."""
+    tx, ty, tz, x, y, z, w = (float(v) for v in vec)
+    n = math.sqrt(x * x + y * y + z * z + w * w)
+    if not n > 0:
+        raise ValueError(f"a pose has the zero quaternion: {list(vec)}")
+    x, y, z, w = x / n, y / n, z / n, w / n
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), tx],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w), ty],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y), tz],
+                     [0.0, 0.0, 0.0, 1.0]], np.float64)
+
+
+def load_camera(path):
+    """The mapping of a camera.yaml / configs/data/*.yaml: {'dataset_name': ..., 'camera_params': {...}}."""
+    yaml = _need("yaml", "PyYAML")
+    with open(path) as fh:
+        cfg = yaml.safe_load(fh)
+    if not isinstance(cfg, dict) or "camera_params" not in cfg:
+        raise ValueError(f"{path} holds no camera_params")
+    if cfg.get("inherit_from") is not None:
+        raise ValueError(f"{path}: inherit_from is not supported; write the camera parameters into one file")
+    return cfg
+
+
+def associate(t_color, t_depth, t_pose, max_dt=MAX_DT, frame_rate=FRAME_RATE):
+    """[(i, j, k)]: for every colour stamp the nearest depth and the nearest pose, each less than max_dt away, then thinned so
+    that the colour stamps of successive entries are more than 1 / frame_rate apart."""
+    t_color, t_depth, t_pose = (np.asarray(t, np.float64) for t in (t_color, t_depth, t_pose))
+    pairs = []
+    for i, t in enumerate(t_color):
+        j, k = int(np.argmin(np.abs(t_depth - t))), int(np.argmin(np.abs(t_pose - t)))
+        if abs(t_depth[j] - t) < max_dt and abs(t_pose[k] - t) < max_dt:
+            pairs.append((i, j, k))
+    kept = pairs[:1]
+    for p in pairs[1:]:
+        if t_color[p[0]] - t_color[kept[-1][0]] > 1.0 / frame_rate:
+            kept.append(p)
+    return kept
+
+
+def _rows(path):
+    """The whitespace-separated fields of every line that is neither empty nor a comment."""
+    with open(path) as fh:
+        return [ln.split() for ln in fh if ln.strip() and not ln.lstrip().startswith("#")]
+
+
+class RecordedSequence:
+    """What the three readers share: the camera, the frame selection and the decoding of one frame."""
+
+    def __init__(self, camera, color_paths, depth_paths, poses, start=0, end=-1, stride=1):
+        camera = camera.get("camera_params", camera)
+        for key in ("image_height", "image_width", "fx", "fy", "cx", "cy", "png_depth_scale"):
+            if key not in camera:
+                raise ValueError(f"the camera parameters lack {key!r}")
+        self.size = (int(camera["image_width"]), int(camera["image_height"]))
+        self.intrinsics = tuple(float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+        self.png_depth_scale = float(camera["png_depth_scale"])
+        self.crop_edge = camera.get("crop_edge")  # read, never applied
+        self.distortion = None
+        if camera.get("distortion") is not None:
+            d = [float(v) for v in camera["distortion"]]
+            if len(d) not in (4, 5):
+                raise ValueError(f"distortion must hold k1 k2 p1 p2 [k3], got {len(d)} values")
+            self.distortion = tuple(d + [0.0] * (5 - len(d)))
+        start, end, stride = int(start), int(end), 1 if stride is None else int(stride)
+        if start < 0:
+            raise ValueError(f"start must not be negative, got {start}")
+        if not (end == -1 or end > start):
+            raise ValueError(f"end ({end}) must be -1 (all frames) or greater than start ({start})")
+        if stride < 1:
+            raise ValueError(f"stride must be >= 1, got {stride}")
+        if len(color_paths) != len(depth_paths):
+            raise ValueError(f"the numbers of colour ({len(color_paths)}) and depth ({len(depth_paths)}) images must be the same")
+        if len(poses) < len(color_paths):
+            raise ValueError(f"{len(color_paths)} frames but only {len(poses)} poses")
+        pick = slice(start, len(color_paths) if end == -1 else end, stride)
+        self.color_paths, self.depth_paths = list(color_paths)[pick], list(depth_paths)[pick]
+        self.poses = [np.asarray(p, np.float64).reshape(4, 4) for p in list(poses)[:len(color_paths)][pick]]
+        self.retained = list(range(len(color_paths)))[pick]  # the indices of the kept frames in the unselected lists
+        if not self.color_paths:
+            raise ValueError("the selection holds no frame")
+        self._depth_size = None
+
+    def __len__(self):
+        return len(self.color_paths)
+
+    @property
+    def depth_size(self):
+        """(Wd, Hd) of the first depth image (its header only is read)."""
+        if self._depth_size is None:
+            Image = _need("PIL.Image", "Pillow")
+            with Image.open(self.depth_paths[0]) as im:
+                self._depth_size = (int(im.size[0]), int(im.size[1]))
+        return self._depth_size
+
+    def frame(self, k):
+        """(color_u8 [Hc,Wc,3] uint8, depth [Hd,Wd] uint16, gt_c2w float32 [4,4]) of frame k, as stored."""
+        Image = _need("PIL.Image", "Pillow")
+        with Image.open(self.color_paths[k]) as im:
+            color = np.array(im.convert("RGB"), np.uint8)  # a copy: torch wants writable memory
+        if (color.shape[1], color.shape[0]) != self.size:
+            raise ValueError(f"{self.color_paths[k]} is {color.shape[1]} x {color.shape[0]}, the camera says {self.size[0]} x {self.size[1]}")
+        with Image.open(self.depth_paths[k]) as im:
+            depth = np.asarray(im)
+        if depth.ndim != 2 or depth.dtype.kind not in "ui" or int(depth.min()) < 0 or int(depth.max()) > 65535:
+            raise ValueError(f"{self.depth_paths[k]} is not a single-channel 16-bit depth image")
+        if (depth.shape[1], depth.shape[0]) != self.depth_size:
+            raise ValueError(f"{self.depth_paths[k]} is {depth.shape[1]} x {depth.shape[0]}, the first depth image {self.depth_size}")
+        return (torch.from_numpy(np.ascontiguousarray(color)), torch.from_numpy(np.ascontiguousarray(depth).astype(np.uint16)),
+                torch.from_numpy(self.poses[k]).float())
+
+    def __iter__(self):
+        return (self.frame(k) for k in range(len(self)))
+
+
+class ReplicaSequence(RecordedSequence):
+    """<basedir>/<sequence>/results/frame*.jpg and depth*.png in natural order; traj.txt: one row-major 4x4 camera-to-world pose
+    per line, line i for frame i."""
+
+    def __init__(self, basedir, sequence, camera, start=0, end=-1, stride=1):
+        folder = os.path.join(basedir, sequence)
+        colors = natural_glob(os.path.join(folder, "results", "frame*.jpg"))
+        depths = natural_glob(os.path.join(folder, "results", "depth*.png"))
+        poses = [np.array([float(v) for v in row], np.float64) for row in _rows(os.path.join(folder, "traj.txt"))]
+        if any(p.size != 16 for p in poses):
+            raise ValueError(f"{folder}/traj.txt: every line must hold 16 numbers")
+        super().__init__(camera, colors, depths, poses, start, end, stride)
+
+
+class TUMSequence(RecordedSequence):
+    """<basedir>/<sequence>/rgb.txt and depth.txt (stamp, file), groundtruth.txt or pose.txt (stamp tx ty tz qx qy qz qw, camera to
+    world), associated and thinned by associate()."""
+
+    def __init__(self, basedir, sequence, camera, start=0, end=-1, stride=1):
+        folder = os.path.join(basedir, sequence)
+        pose_list = next((p for p in (os.path.join(folder, n) for n in ("groundtruth.txt", "pose.txt")) if os.path.isfile(p)), None)
+        if pose_list is None:
+            raise ValueError(f"{folder} holds neither groundtruth.txt nor pose.txt")
+        rgb, dep, pos = _rows(os.path.join(folder, "rgb.txt")), _rows(os.path.join(folder, "depth.txt")), _rows(pose_list)
+        stamps = lambda rows: [float(r[0]) for r in rows]
+        self.associations = associate(stamps(rgb), stamps(dep), stamps(pos))
+        colors = [os.path.join(folder, rgb[i][1]) for i, _, _ in self.associations]
+        depths = [os.path.join(folder, dep[j][1]) for _, j, _ in self.associations]
+        poses = [quaternion_pose(pos[k][1:8]) for _, _, k in self.associations]
+        super().__init__(camera, colors, depths, poses, start, end, stride)
+
+
+class ScanNetSequence(RecordedSequence):
+    """<basedir>/<sequence>/color/*.jpg, depth/*.png and pose/*.txt (one 4x4 camera-to-world per file), each in natural order.
+    The colour and depth sizes differ (1296 x 968 against 640 x 480).  ignore_bad: drop the selected frames whose pose is not
+    finite."""
+
+    def __init__(self, basedir, sequence, camera, start=0, end=-1, stride=1, ignore_bad=False):
+        folder = os.path.join(basedir, sequence)
+        colors = natural_glob(os.path.join(folder, "color", "*.jpg"))
+        depths = natural_glob(os.path.join(folder, "depth", "*.png"))
+        poses = [np.loadtxt(p, dtype=np.float64) for p in natural_glob(os.path.join(folder, "pose", "*.txt"))]
+        if any(p.size != 16 for p in poses):
+            raise ValueError(f"{folder}/pose: every file must hold a 4x4 matrix")
+        super().__init__(camera, colors, depths, poses, start, end, stride)
+        if ignore_bad:
+            good = [k for k, p in enumerate(self.poses) if np.isfinite(p).all()]
+            if not good:
+                raise ValueError("no selected frame has a finite pose")
+            for name in ("color_paths", "depth_paths", "poses", "retained"):
+                setattr(self, name, [getattr(self, name)[k] for k in good])
+
+
+READERS = {"replica": ReplicaSequence, "tum": TUMSequence, "scannet": ScanNetSequence}
+
+
+def working_size(data_cfg):
+    """(W, H) from desired_image_width / desired_image_height of a `data` section, or None when it names neither."""
+    if "desired_image_width" not in data_cfg and "desired_image_height" not in data_cfg:
+        return None
+    return int(data_cfg["desired_image_width"]), int(data_cfg["desired_image_height"])
+
+
+def open_sequence(data_cfg):
+    """A reader from the `data` section of a reference configuration: gradslam_data_cfg (the camera file, which also names the
+    dataset; without it dataset_name of the section itself), basedir, sequence (its last path component), start, end, stride,
+    ignore_bad.  desired_image_width / height do not touch the reader: working_size() hands them to config['cameras']."""
+    if "gradslam_data_cfg" in data_cfg:
+        cam = load_camera(data_cfg["gradslam_data_cfg"])
+    else:
+        cam = {"dataset_name": data_cfg.get("dataset_name"), "camera_params": data_cfg.get("camera_params", {})}
+    name = str(cam.get("dataset_name", data_cfg.get("dataset_name"))).lower()
+    if name not in READERS:
+        raise ValueError(f"unknown dataset name {name!r}; known: {', '.join(KNOWN)}")
+    for key in ("basedir", "sequence"):
+        if key not in data_cfg:
+            raise ValueError(f"the data section lacks {key!r}")
+    kw = dict(start=data_cfg.get("start", 0), end=data_cfg.get("end", -1), stride=data_cfg.get("stride", 1))
+    if name == "scannet":
+        kw["ignore_bad"] = bool(data_cfg.get("ignore_bad", False))
+    return READERS[name](str(data_cfg["basedir"]), os.path.basename(str(data_cfg["sequence"])), cam["camera_params"], **kw)

@@ -2,6 +2,9 @@
 every definition):
 
     gt_color, gt_depth = ingest(color_u8, depth, png_depth_scale, size=(W, H))   # sensor frame -> working tensors, one launch
+    gt_color, gt_depth = ingest_ex(color_u8, depth, png_depth_scale, size=(W, H), distortion=(k1, k2, p1, p2, k3),
+                                   intrinsics=(fx, fy, cx, cy))                  # the same for a depth image of another size and /
+                                                                                 # or a distorted colour image (libgs2d_ingest_hip.so)
     state = FrameState(device)
     d = state.decide(stats, opt.w2c, numel=H * W, n_local_frames=n, map_size=P, cfg=config["frontend"])
     if d.keyframe: ...                                                           # the frame's ONE new host read
@@ -16,12 +19,13 @@ PoseOptimizer builds its pose from a unit quaternion.
 
 No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError before anything is launched."""
 import ctypes as C
+import math
 import struct
 from collections import namedtuple
 
 import torch
 
-from . import _front_lib
+from . import _front_lib, _ingest_lib
 from ._check import check_device, check_tensor, check_vector, require
 from ._host import on_device as _on_device
 from .rasterizer import GaussianRasterizationSettings
@@ -62,6 +66,45 @@ def ingest(color_u8, depth, png_depth_scale, size=None):
     gt_depth = torch.empty((H, W), dtype=torch.float32, device=dev)
     _front_lib.call("gs2d_front_ingest", dev, W0, H0, color_u8.data_ptr(), depth.data_ptr(), _DEPTH_KINDS[depth.dtype], scale, W, H,
                     gt_color.data_ptr(), gt_depth.data_ptr())
+    return gt_color, gt_depth
+
+
+def ingest_ex(color_u8, depth, png_depth_scale, size=None, distortion=None, intrinsics=None):
+    """ingest() for recorded sensors (gs2d_ingest_ex, include/gs2d_ingest.h: one launch, no host read).
+    color_u8: uint8 [Hc,Wc,3]; depth: [Hd,Wd] uint16 (int16 storage is read as uint16) or float32, with a size of its own; size:
+    the target (W, H), None for the colour's; distortion: None or (k1, k2, p1, p2, k3), then with intrinsics = (fx, fy, cx, cy) or
+    a 3x3 AT THE COLOUR'S SIZE, host values.  Returns (gt_color float32 [H,W,3], gt_depth float32 [H,W]).  Depth is nearest at the
+    depth's own size and never undistorted.  Without distortion the colour is ingest()'s (equal sizes: the same bits); with it
+    the colour is one bilinear sample at the target pixel's centre carried through the Brown-Conrady model, and a tap outside
+    the image contributes 0."""
+    require(isinstance(color_u8, torch.Tensor) and color_u8.dtype == torch.uint8 and color_u8.dim() == 3 and color_u8.shape[2] == 3,
+            "color_u8 must be a uint8 [H,W,3] tensor")
+    Hc, Wc = int(color_u8.shape[0]), int(color_u8.shape[1])
+    require(Hc >= 1 and Wc >= 1 and Hc * Wc <= 1 << 30, "color_u8 must have 1 <= H*W <= 2^30 pixels")
+    require(isinstance(depth, torch.Tensor) and depth.dtype in _DEPTH_KINDS, "depth must be a uint16, int16 or float32 tensor")
+    require(depth.dim() == 2, f"depth must be [H,W], got {tuple(depth.shape)}")
+    Hd, Wd = int(depth.shape[0]), int(depth.shape[1])
+    require(Hd >= 1 and Wd >= 1 and Hd * Wd <= 1 << 30, "depth must have 1 <= H*W <= 2^30 pixels")
+    require(color_u8.is_contiguous() and depth.is_contiguous(), "color_u8 and depth must be contiguous")
+    scale = float(png_depth_scale)
+    require(scale > 0 and scale != float("inf"), f"png_depth_scale must be finite and > 0, got {png_depth_scale!r}")
+    W, H = (Wc, Hc) if size is None else (int(size[0]), int(size[1]))
+    require(W >= 1 and H >= 1 and W * H <= 1 << 30, f"size must be (W, H) with 1 <= W*H <= 2^30, got {size!r}")
+    lens = [0.0] * 5 + [1.0, 1.0, 0.0, 0.0]
+    if distortion is not None:
+        require(intrinsics is not None, "distortion needs the intrinsics (fx, fy, cx, cy) at the colour's size")
+        coeff = [float(v) for v in distortion]
+        require(len(coeff) == 5, f"distortion must be (k1, k2, p1, p2, k3), got {len(coeff)} values")
+        lens = coeff + list(_intrinsics4(intrinsics))
+        require(all(math.isfinite(v) for v in lens), f"distortion and intrinsics must be finite, got {lens}")
+        require(lens[5] > 0 and lens[6] > 0, f"fx, fy must be > 0, got {lens[5]!r}, {lens[6]!r}")
+    check_device(None, (color_u8, "color_u8"))
+    dev = color_u8.device
+    check_device(dev, (depth, "depth"))
+    gt_color = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    gt_depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    _ingest_lib.call("gs2d_ingest_ex", dev, Wc, Hc, color_u8.data_ptr(), Wd, Hd, depth.data_ptr(), _DEPTH_KINDS[depth.dtype], scale, W, H,
+                     int(distortion is not None), *lens, gt_color.data_ptr(), gt_depth.data_ptr())
     return gt_color, gt_depth
 
 

@@ -4,6 +4,7 @@
     result = run_slam(sequence, config, seed=0)
     result.trajectory(), result.gt_trajectory()      # [N,4,4] world-to-camera, on the device
     result.evaluate()                                 # evaluate.evaluate_map over the saved frames, with the ATE
+    result.save(directory, data=..., seed=0)          # results.json, traj_est.txt, traj_gt.txt, map.ply (gaus_slam_amd/run.py)
 
 `config` is a dict with the reference's key names (configs/*/config*.py); check_config() lists what is read and refuses, by name,
 what the driver does not wire.  The per-frame path reads the host where the reference's control flow needs it and nowhere else:
@@ -14,6 +15,8 @@ the device (frontend_ops).
 Departures from the reference: the covisible submaps come from the geometric keyframe bank (covis.py), not NetVLAD; inverses of
 poses are the rigid closed form; process_final() passes the frontend's tracking flag on, which the reference drops there; the
 frame that closes a tracked frame is rendered with the fused tracking render, not Renderer_view."""
+import json
+import os
 import random
 from collections import OrderedDict
 
@@ -424,9 +427,69 @@ class Backend(_Base):
         return OrderedDict((n, t.detach().clone()) for n, t in leaves.items())
 
 
+def write_trajectory(path, w2cs):
+    """World-to-camera poses [N,4,4] as the layout of a Replica traj.txt: camera to world, one row-major 4x4 per line.  The
+    inverse is the rigid closed form, in float64 on the host; 17 significant digits, so float32 poses come back exactly."""
+    w2cs = torch.as_tensor(w2cs).detach().cpu().double().reshape(-1, 4, 4)
+    c2w = torch.zeros_like(w2cs)
+    R, t = w2cs[:, :3, :3], w2cs[:, :3, 3]
+    c2w[:, :3, :3] = R.transpose(1, 2)
+    c2w[:, :3, 3] = -(R.transpose(1, 2) @ t[:, :, None])[:, :, 0]
+    c2w[:, 3, 3] = 1.0
+    with open(path, "w") as fh:
+        for m in c2w.reshape(-1, 16).tolist():
+            fh.write(" ".join(repr(v) for v in m) + "\n")
+
+
+def write_map(path, params):
+    """The raw parameters (means3D, opacities, scales, rotations, colors: [P,k] tensors) as the reference's map.ply
+    (ply.save_ply)."""
+    from . import ply
+    host = {n: params[n].detach().cpu().numpy() for n in ("means3D", "opacities", "scales", "rotations", "colors")}
+    ply.save_ply(path, host["means3D"], host["opacities"], host["scales"], host["rotations"], rgb=host["colors"])
+
+
+def write_results(path, evaluation, stamps, data=None, seed=None):
+    """results.json: the evaluation (tensors and arrays as lists), the build stamps of the libraries used, the configuration's
+    `data` section and the seed."""
+    def plain(v):
+        if isinstance(v, torch.Tensor):
+            return v.detach().cpu().tolist()
+        if hasattr(v, "tolist"):
+            return v.tolist()
+        if isinstance(v, dict):
+            return {str(k): plain(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [plain(x) for x in v]
+        return v if isinstance(v, (bool, int, float, str, type(None))) else str(v)
+    with open(path, "w") as fh:
+        json.dump(dict(evaluation=plain(evaluation), build=plain(stamps), data=plain(data), seed=seed), fh, indent=1)
+        fh.write("\n")
+
+
+def build_stamps():
+    """build_info() of the libraries a run of the driver loads: rasterizer, map, loss, covisibility, frontend, ingest."""
+    from . import _covis_lib, _front_lib, _ingest_lib, _lib, _loss_lib, _map_lib
+    return OrderedDict((name, mod.build_info()) for name, mod in (("rasterizer", _lib), ("map", _map_lib), ("loss", _loss_lib),
+                                                                  ("covis", _covis_lib), ("front", _front_lib), ("ingest", _ingest_lib)))
+
+
 class SlamResult:
     def __init__(self, frontend, backend, records):
         self.frontend, self.backend, self.records = frontend, backend, records
+
+    def save(self, directory, evaluation=None, data=None, seed=None):
+        """Writes results.json (write_results: `evaluation`, or evaluate() when None), traj_est.txt and traj_gt.txt (camera to
+        world, the layout of traj.txt) and map.ply (the global map's raw parameters) into `directory`: the tail of the
+        reference's scripts/gaus.py.  Returns the evaluation."""
+        os.makedirs(directory, exist_ok=True)
+        if evaluation is None:
+            evaluation = self.evaluate()
+        write_results(os.path.join(directory, "results.json"), evaluation, build_stamps(), data, seed)
+        write_trajectory(os.path.join(directory, "traj_est.txt"), self.trajectory())
+        write_trajectory(os.path.join(directory, "traj_gt.txt"), self.gt_trajectory())
+        write_map(os.path.join(directory, "map.ply"), self.backend.map.soa.views)
+        return evaluation
 
     def trajectory(self):
         return self.backend.trajectory()
@@ -455,7 +518,9 @@ def run_slam(sequence, config, seed=0, device="cuda"):
     """The loop of scripts/gaus.py:84-104 over `sequence`: any iterable of (color_u8 [H0,W0,3] uint8, depth [H0,W0] uint16 or
     float32, gt_c2w [4,4]) with the attributes intrinsics (fx, fy, cx, cy at the source size), png_depth_scale and size (W0, H0).
     config['cameras'] height / width give the working size and its intrinsics are filled in from the sequence's, scaled, when
-    absent.  Ground-truth poses are taken relative to the first frame.  Returns a SlamResult."""
+    absent.  Ground-truth poses are taken relative to the first frame.  A sequence with a `distortion` that is not None, or a
+    `depth_size` other than its size (gaus_slam_amd/datasets.py), goes through frontend_ops.ingest_ex; every other sequence
+    through ingest, as before.  Returns a SlamResult."""
     config = dict(config)
     config["cameras"] = cam = dict(config.get("cameras", {}))
     W0, H0 = sequence.size
@@ -469,10 +534,16 @@ def run_slam(sequence, config, seed=0, device="cuda"):
     frontend, backend = Frontend(config, rng, device), Backend(config, rng, device)
     dev = frontend.device
     records, first_w2c = [], None
+    distortion = getattr(sequence, "distortion", None)
+    extended = distortion is not None or tuple(getattr(sequence, "depth_size", None) or (W0, H0)) != (W0, H0)
     for time_idx, (color_u8, depth, gt_c2w) in enumerate(sequence):
         if depth.dtype == torch.uint16:  # the same bits under a dtype every copy supports; ingest reads int16 storage as uint16
             depth = depth.view(torch.int16)
-        gt_color, gt_depth = _ops.ingest(color_u8.to(dev), depth.to(dev), sequence.png_depth_scale, size)
+        if extended:
+            gt_color, gt_depth = _ops.ingest_ex(color_u8.to(dev), depth.to(dev), sequence.png_depth_scale, size, distortion=distortion,
+                                                intrinsics=sequence.intrinsics)
+        else:
+            gt_color, gt_depth = _ops.ingest(color_u8.to(dev), depth.to(dev), sequence.png_depth_scale, size)
         gt_c2w = gt_c2w.to(dev, torch.float32).contiguous()
         if first_w2c is None:
             first_w2c = _ops.compose(gt_c2w, inv_a=True)
