@@ -12,7 +12,7 @@ EXPORTS = ["gs2d_forward", "gs2d_backward", "gs2d_forward_posed", "gs2d_backward
            "gs2d_image_layout", "gs2d_last_error", "gs2d_build_info", "gs2d_stage_timing_enable",
            "gs2d_stage_timing_read", "gs2d_slam_loss", "gs2d_adam_step", "gs2d_pose_quat", "gs2d_backward_staged", "gs2d_set_deterministic",
            "gs2d_get_deterministic", "gs2d_set_reference_binning", "gs2d_get_reference_binning", "gs2d_set_launch_ahead", "gs2d_get_launch_ahead", "gs2d_forward_batch",
-           "gs2d_backward_batch", "gs2d_stage_timing_read_abs"]
+           "gs2d_backward_batch", "gs2d_stage_timing_read_abs", "gs2d_binning_contrib_offset"]
 MAX_FRAMES = 8  # GS2D_MAX_FRAMES
 
 
@@ -74,7 +74,7 @@ def lib():
     L.gs2d_mark_visible.argtypes = [i, vp, vp, vp, vp, vp]
     L.sknn_dist2.restype = i
     L.sknn_dist2.argtypes = [i, vp, vp, ALLOC_FN, vp, vp]
-    for n in ("gs2d_geometry_bytes", "gs2d_binning_bytes"):
+    for n in ("gs2d_geometry_bytes", "gs2d_binning_bytes", "gs2d_binning_contrib_offset"):
         getattr(L, n).restype = sz
         getattr(L, n).argtypes = [i]
     L.gs2d_image_bytes.restype = sz

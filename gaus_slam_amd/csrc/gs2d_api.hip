@@ -237,6 +237,7 @@ void gs2d_binning_layout(int R, size_t o[2])
     const BinLayout L = bin_layout(R);
     o[0] = L.point_list; o[1] = L.keys;  // (L.hits is internal)
 }
+size_t gs2d_binning_contrib_offset(int R) { return bin_layout(R, g_deterministic.load() != 0).contrib; }
 void gs2d_image_layout(int width, int height, size_t o[2])
 {
     const ImgLayout L = img_layout(width, height);
@@ -487,7 +488,7 @@ int fwd_phase_b(const FwdShared& c, FwdFrame& f, int slot, bool allow_ahead = tr
             f.bin = bin_pre;
             f.bf.ranges = ranges; f.bf.point_list = nullptr; f.bf.rec = (const float4*)(geom + GL.rec);
             f.bf.out_color = f.out_color; f.bf.out_others = f.out_others; f.bf.pix_state = (float*)(img + IL.pix);
-            f.bf.hits = nullptr; f.bf.hits4 = nullptr; f.bf.zero = (float4*)(geom + GL.grad_rec);
+            f.bf.hits = nullptr; f.bf.hits4 = nullptr; f.bf.contrib = nullptr; f.bf.zero = (float4*)(geom + GL.grad_rec);
             f.bf.keys = nullptr; f.bf.keys_alt = nullptr; f.bf.vals_alt = nullptr;
             f.bf.dev = db;
             return 0;
@@ -567,7 +568,7 @@ int fwd_phase_b(const FwdShared& c, FwdFrame& f, int slot, bool allow_ahead = tr
     }
     f.bf.ranges = ranges; f.bf.point_list = point_list; f.bf.rec = (const float4*)(geom + GL.rec);
     f.bf.out_color = f.out_color; f.bf.out_others = f.out_others; f.bf.pix_state = (float*)(img + IL.pix);
-    f.bf.hits = (uint8_t*)(bin + BL.hits); f.bf.hits4 = (uint8_t*)(bin + BL.hits4);
+    f.bf.hits = (uint8_t*)(bin + BL.hits); f.bf.hits4 = (uint8_t*)(bin + BL.hits4); f.bf.contrib = (uint8_t*)(bin + BL.contrib);
     f.bf.zero = (float4*)(geom + GL.grad_rec);
     f.bf.keys = keys; f.bf.keys_alt = keys_alt; f.bf.vals_alt = vals_alt;
     f.bf.dev = gs2d::DevBin{nullptr, nullptr, 0u, 0};
@@ -687,7 +688,7 @@ int fwd_batch_fused(const FwdShared& c, FwdFrame* f, int K)
         gs2d::BlendFwdFrame& o = f[k].bf;
         o.ranges = b.ranges; o.point_list = b.point_list; o.rec = (const float4*)(f[k].geom + GL.rec);
         o.out_color = f[k].out_color; o.out_others = f[k].out_others; o.pix_state = (float*)(f[k].img + IL.pix);
-        o.hits = (uint8_t*)(bn + BL.hits); o.hits4 = (uint8_t*)(bn + BL.hits4);
+        o.hits = (uint8_t*)(bn + BL.hits); o.hits4 = (uint8_t*)(bn + BL.hits4); o.contrib = (uint8_t*)(bn + BL.contrib);
         o.zero = (float4*)(f[k].geom + GL.grad_rec);
         o.keys = b.keys; o.keys_alt = b.keys_alt; o.vals_alt = b.vals_alt;
         o.dev = gs2d::DevBin{nullptr, nullptr, 0u, 0};
@@ -936,7 +937,9 @@ int gs2d_backward_staged(int stages, int g_begin, int g_end, int P, int D, int M
     const uint8_t* clamped = (const uint8_t*)(geom_buffer + GL.clamped);
     float* grad_rec = (float*)(geom_buffer + GL.grad_rec);
     const uint32_t* point_list = (const uint32_t*)(binning_buffer + BL.point_list);
-    const uint8_t* hits = (const uint8_t*)(binning_buffer + BL.hits4);  // the backward reads the row bits (one byte per quadrant)
+    const uint8_t* hits = (const uint8_t*)(binning_buffer + BL.hits4);  // the row bits of the cull: which slots det_reduce sums
+    // the blend kernels build their queues from what the forward composited (one byte of half-row bits per quadrant)
+    const uint8_t* contrib = (const uint8_t*)(binning_buffer + BL.contrib);
     const uint2* ranges = (const uint2*)(img_buffer + IL.ranges);
     const float* pix_state = (const float*)(img_buffer + IL.pix);
 
@@ -945,8 +948,8 @@ int gs2d_backward_staged(int stages, int g_begin, int g_end, int P, int D, int M
             GS2D_CHECK(hipMemsetAsync(grad_rec, 0, sizeof(float) * GS2D_GRAD_FLOATS * (size_t)P, s), "memset grad_rec");
         if (R > 0) {
             g_timer.begin(ST_BLEND_BWD, s);
-            const gs2d::BlendBwdFrame bf = {ranges, point_list, rec, pix_state, hits, dL_dpix, dL_depths, grad_rec, nullptr,
-                                            (const uint16_t*)(binning_buffer + BL.hits), pose_fast ? grad_rec + 4 * (size_t)P : nullptr};
+            const gs2d::BlendBwdFrame bf = {ranges, point_list, rec, pix_state, contrib, dL_dpix, dL_depths, grad_rec, nullptr,
+                                            pose_fast ? grad_rec + 4 * (size_t)P : nullptr};
             gs2d::launch_blend_bwd(width, height, 1, &bf, background, use_sa, dL_dpose, pose_floats, s);
             g_timer.end(ST_BLEND_BWD, s);
             GS2D_STAGE("blend_bwd");
@@ -960,8 +963,7 @@ int gs2d_backward_staged(int stages, int g_begin, int g_end, int P, int D, int M
         g_timer.begin(ST_BLEND_BWD, s);
         if (R > 0) {
             GS2D_CHECK(hipMemsetAsync(det_slots, 0, sizeof(float) * GS2D_GRAD_FLOATS * 4 * (size_t)R, s), "memset det_slots");
-            const gs2d::BlendBwdFrame bf = {ranges, point_list, rec, pix_state, hits, dL_dpix, dL_depths, grad_rec, det_slots,
-                                            (const uint16_t*)(binning_buffer + BL.hits), nullptr};
+            const gs2d::BlendBwdFrame bf = {ranges, point_list, rec, pix_state, contrib, dL_dpix, dL_depths, grad_rec, det_slots, nullptr};
             gs2d::launch_blend_bwd(width, height, 1, &bf, background, use_sa, nullptr, 0, s);
         }
         gs2d::launch_det_reduce(P, R, width, height, ranges, point_list, (const ushort4*)(geom_buffer + GL.rect),
@@ -1038,9 +1040,8 @@ int gs2d_backward_batch(int K, const gs2d_frame_grad* fr, int accumulate, int P,
             b.point_list = (const uint32_t*)(f.binning_buffer + BL.point_list);
             b.rec = (const float4*)(f.geom_buffer + GL.rec);
             b.pix_state = (const float*)(f.img_buffer + IL.pix);
-            b.hits = (const uint8_t*)(f.binning_buffer + BL.hits4);
+            b.contrib = (const uint8_t*)(f.binning_buffer + BL.contrib);
             b.dL_dpix = f.dL_dpix; b.dL_dothers = f.dL_depths; b.grad_rec = grad_rec; b.det_slots = nullptr; b.dense_m2d = nullptr;
-            b.hits16 = (const uint16_t*)(f.binning_buffer + BL.hits);
         }
     }
     if (nb > 0) {

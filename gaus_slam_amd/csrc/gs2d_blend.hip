@@ -25,11 +25,8 @@
 #endif
 #ifndef GS2D_BWD_POSE_GROUPS
 #define GS2D_BWD_POSE_GROUPS 8  // ... of the pose-only backward (its accumulators are per row: no LDS atomics to eat the trips
-                                // eight queues save; it derives its half-row cull bits from the forward's group bits itself)
+                                // eight queues save; it takes the forward's eight contribution bits as they are)
 #endif
-// eight queues in the FULL backward (experiment builds): the forward's phase 0 stores eight half-row cull bits per (instance,
-// quadrant) instead of four row bits
-#define GS2D_HALFROW_BITS (GS2D_BWD_GROUPS == 8)
 #ifndef GS2D_BWD_LANE_CLASH
 #define GS2D_BWD_LANE_CLASH 1   // four queues, full backward: the LDS-atomic fallback of the accumulate is decided per LANE (a flag in
                                 // bit 6 of the queue entry) instead of per trip: 0.2385 -> 0.2331 ms (profiles/bwd_queue_ab_r04.txt);
@@ -141,7 +138,8 @@ struct FwdBatch {
     uint32_t tail[4];           // the pipeline reads up to two entries past a full queue (values unused)
     uint16_t tm[64];            // group bits of the staged splats
     uint32_t sid[64];           // Gaussian id and list position of the staged splats: a batch's slots are handed out chunk by
-    uint32_t spos[64];          // chunk, its records are gathered in ONE round trip afterwards
+    uint32_t spos[64];          // chunk, its records are gathered in ONE round trip afterwards.  From then on sid[slot] is the
+                                // slot's CONTRIBUTION word: the half-row bits (gs2d_cull.h) of the groups that composited the splat
 };
 
 // XCD-aware workgroup -> tile mapping.  Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8), each with its own
@@ -240,6 +238,7 @@ blend_fwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
     float* __restrict__ pix_state = fa->pix_state;
     uint8_t* hits = fa->hits;    /* written by phase 0: neither const nor restrict */
     uint8_t* hits4 = fa->hits4;
+    uint8_t* contrib = fa->contrib;  /* cleared by phase 0, then every wave stores the bytes of its own quadrant */
     float4* __restrict__ zero = fa->zero;
     uint64_t* sort_keys = fa->keys; uint64_t* sort_keys_alt = fa->keys_alt; uint32_t* sort_vals_alt = fa->vals_alt;
     uint32_t* sort_list = fa->point_list;
@@ -252,7 +251,7 @@ blend_fwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
         const BinLayout BL = bin_layout((int)Rd, fa->dev.det != 0, (int)fa->dev.cap);
         char* bb = fa->dev.base;
         sort_list = (uint32_t*)(bb + BL.point_list); point_list = sort_list;
-        hits = (uint8_t*)(bb + BL.hits); hits4 = (uint8_t*)(bb + BL.hits4);
+        hits = (uint8_t*)(bb + BL.hits); hits4 = (uint8_t*)(bb + BL.hits4); contrib = (uint8_t*)(bb + BL.contrib);
         sort_keys = (uint64_t*)(bb + BL.keys); sort_keys_alt = (uint64_t*)(bb + BL.keys_alt); sort_vals_alt = (uint32_t*)(bb + BL.vals_alt);
     }
     const int tile = xcd_tile(local_block, ntiles);
@@ -288,12 +287,13 @@ blend_fwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
     // workgroup share the CU's write-through vector cache, so after the release / barrier / acquire the plain loads
     // below see the stores (an agent-scope fence would write back the XCD's whole L2 from every workgroup)
     cull_tile_list(range, (float)(tx * GS2D_TILE), (float)(ty * GS2D_TILE), point_list, rec,
-                   reinterpret_cast<uint64_t*>(hits), reinterpret_cast<uint32_t*>(hits4));
+                   reinterpret_cast<uint64_t*>(hits), reinterpret_cast<uint32_t*>(hits4), reinterpret_cast<uint32_t*>(contrib));
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
     const uint8_t* qrow = wb.ql[row];
+    const uint32_t my_halfrow = halfrow_bit_of_group(row);  // this quad's bit in a splat's contribution byte
     // the bytes behind the queues (the pipeline reads up to two entries past a full queue): wave-private, written once (the
     // LDS was the depth sort's until the barrier above)
     if (lane < 4) wb.tail[lane] = 0x40404040u;
@@ -362,10 +362,11 @@ blend_fwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
             const float4* rp = rec + (size_t)wb.sid[lane] * GS2D_REC_F4;
             const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
             float4 r4 = rp[4];
-            r4.w = __uint_as_float(wb.spos[lane]);
+            r4.z = __uint_as_float((uint32_t)lane);  // the slot number rides in the record (rho_max is cull-only): the trip loop
+            r4.w = __uint_as_float(wb.spos[lane]);   // finds the slot's contribution word without keeping its queue entry
             wb.q(0)[lane] = r0; wb.q(1)[lane] = r1; wb.q(2)[lane] = r2; wb.q(3)[lane] = r3; wb.q(4)[lane] = r4;
         }
-        if (fill == 0) break;  // list exhausted
+        wb.sid[lane] = 0u;  // the id is in flight (or the slot is empty): the word now collects the slot's contribution bits
         wave_lds_sync();
         // the sixteen group queues: slot numbers of the splats whose bit r is set, in slot (= depth) order, ended by 255
         reinterpret_cast<uint4*>(&wb.ql[0][0])[lane] = make_uint4(0x40404040u, 0x40404040u, 0x40404040u, 0x40404040u);
@@ -415,7 +416,18 @@ blend_fwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
             const uint64_t pass_m = ok_m & ballot64(live_) & ~done_m;                                                \
             const uint64_t stop_m = pass_m & ballot64(test_T < 0.0001f);                                             \
             done_m |= stop_m;                                                                                        \
-            if (__builtin_amdgcn_inverse_ballot_w64(pass_m & ~stop_m)) {                                             \
+            const uint64_t comp_m = pass_m & ~stop_m; /* the lanes that composite this splat */                      \
+            /* Written down for the backward: a quad with a compositing lane ORs its half-row bit into the slot's      \
+               contribution word (one integer LDS OR by the quad's first lane, no return value; the "some lane of the  \
+               quad" mask is formed on the scalar unit).  The backward walks a (row, splat) pair only if a bit of the   \
+               row is set.  Nothing is lost by that: its Part A is fwd_eval's arithmetic and its `contributor <         \
+               last_contributor` is the other half of "composited", so in a pair without a bit every lane is inactive  \
+               and all sums are exact zeros. */                                                                       \
+            uint64_t quad_m = comp_m | (comp_m >> 1);                                                                \
+            quad_m = (quad_m | (quad_m >> 2)) & 0x1111111111111111ull;                                               \
+            if (__builtin_amdgcn_inverse_ballot_w64(quad_m))                                                         \
+                __hip_atomic_fetch_or(&wb.sid[__float_as_uint(C4.z)], my_halfrow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); \
+            if (__builtin_amdgcn_inverse_ballot_w64(comp_m)) {                                                       \
                 const float w = alpha * T;                                                                           \
                 const uint64_t front_m = ballot64(T > 0.5f);                                                         \
                 if (__builtin_amdgcn_inverse_ballot_w64(front_m)) { median_depth = depth; median_contributor = contributor; } \
@@ -455,6 +467,11 @@ blend_fwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
             GS2D_FWD_STEP(b0, b1, b2, b3, b4, a0, a1, a2, a3, a4, ja, jb)
         }
 #undef GS2D_FWD_STEP
+        // the batch's contribution bytes, one per staged (instance, quadrant) pair -- also when the wave leaves in mid-batch
+        // (every pixel finished): the slots it never reached then store 0, the exact answer.  Byte stores behind phase 0's
+        // barrier (which cleared the words), to bytes no other wave writes.
+        wave_lds_sync();
+        if (lane < fill) contrib[(size_t)(range.x + wb.spos[lane] - 1u) * 4 + wave] = (uint8_t)wb.sid[lane];
     }
     GS2D_PROF_END(0)
     if (inside) {  // forward.cu:441-466
@@ -485,8 +502,9 @@ blend_fwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
 
 // The backward keeps one queue per 4x4 sub-block (16-lane DPP row): finer queues would cut its trips too, but every
 // (group, splat) pair costs 13 LDS float atomics and those run at about half a lane per clock per CU -- with sixteen
-// 2x2 groups the kernel measured 0.59 ms instead of 0.31 ms.  Its four row bits per quadrant are the ORs of the forward's
-// group bits, written next to them by phase 0 of the forward (hits4, rows_from_groups in gs2d_cull.h).
+// 2x2 groups the kernel measured 0.59 ms instead of 0.31 ms.  Its queues are built from the contribution bytes the forward's
+// blend loop leaves (contrib: eight half-row bits per (instance, quadrant), ORed in pairs to four row bits); the cull's own
+// row bits (hits4, rows_from_groups in gs2d_cull.h, written by phase 0) say which deterministic slots exist (gs2d_det.hip).
 
 // ------------------------------------------------------------------------------------------ backward
 template <int CTRL>
@@ -843,8 +861,7 @@ blend_bwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
     const uint32_t* __restrict__ point_list = fa->point_list;
     const float4* __restrict__ rec = fa->rec;
     const float* __restrict__ pix_state = fa->pix_state;
-    const uint8_t* __restrict__ hits = fa->hits;
-    const uint16_t* __restrict__ hits16 = fa->hits16;
+    const uint8_t* __restrict__ contrib = fa->contrib;
     const float* __restrict__ dL_dpix = fa->dL_dpix;
     const float* __restrict__ dL_dothers = fa->dL_dothers;
     float* __restrict__ grad_rec = fa->grad_rec;
@@ -859,11 +876,10 @@ blend_bwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
     const int row = lane >> 4, li = lane & 15;                       // DPP row = 4x4 sub-block (same mapping as the forward)
     const int grp = NG == 8 ? lane >> 3 : row;                       // the queue this lane follows (NG == 8: lanes 0-7 of a row =
     const int grp8 = grp * 8;                                        // its pixel rows 0-1, lanes 8-15 = pixel rows 2-3)
-    // the cull bits of list position `at` for this quadrant, in the form this instantiation's queues want
-    auto cull_bits = [&](uint32_t at) -> uint32_t {
-        if (NG == 8 && !GS2D_HALFROW_BITS) return halfrows_from_groups_fast(hits16[(size_t)at * 4 + wave]);
-        return hits[(size_t)at * 4 + wave];
-    };
+    // the queue bits of list position `at` for this quadrant: the eight half-rows in which some pixel composited the splat in
+    // the forward (blend_fwd_kernel wrote them down, GS2D_FWD_STEP) -- exact where the cull's reach bits and `pos < grp_last`
+    // are both conservative, so fewer (row, splat) pairs are walked with every lane inactive
+    auto cull_bits = [&](uint32_t at) -> uint32_t { return contrib[(size_t)at * 4 + wave]; };
     const uint8_t* qrow = wb.ql[grp];
     const int px = qx0 + (row & 1) * 4 + (li & 3), py = qy0 + (row >> 1) * 4 + (li >> 2);
     const bool inside = px < W && py < H;
@@ -1000,9 +1016,9 @@ blend_bwd_kernel(int W, int H, int gx, int ntiles, int blocks_per_frame, const f
                 if (chunk < 0) break;
                 cb = chunk--;
                 const int n = (int)min(64u, max_last - (uint32_t)cb * 64u);
-                // queues come from the cull bits of this (instance, quadrant): eight half-row bits, ORed to four row bits here
-                // when the wave keeps four queues
-                tm = lane < n ? ((NG == 8 || !GS2D_HALFROW_BITS) ? pf_tm : rows_from_halfrows(pf_tm)) : 0u;
+                // queues come from the contribution bits of this (instance, quadrant): eight half-row bits, ORed to four row
+                // bits here when the wave keeps four queues
+                tm = lane < n ? (NG == 8 ? pf_tm : rows_from_halfrows(pf_tm)) : 0u;
                 my_id = pf_id;
                 const uint32_t nb = min(range.x + (uint32_t)max(chunk, 0) * 64u + lane, last_i);
                 pf_tm = cull_bits(nb);

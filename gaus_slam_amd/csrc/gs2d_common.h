@@ -33,7 +33,7 @@ struct GeomLayout {
     size_t depths, tiles_touched, point_offsets, rec, clamped, scan_tmp, grad_rec, rect, total;
 };
 struct BinLayout {
-    size_t point_list, hits, hits4, keys, vals_alt, keys_alt, hist, det_inv, det_slots, total;
+    size_t point_list, hits, hits4, keys, vals_alt, keys_alt, hist, det_inv, det_slots, contrib, total;
     size_t hist_elems;
 };
 struct ImgLayout {
@@ -102,9 +102,13 @@ __host__ __device__ static inline BinLayout bin_layout(int R, bool det = false, 
             o = gs2d_align_up(o + 4 * n, 256);
             det_slots = o; o = gs2d_align_up(o + 4 * (size_t)GS2D_GRAD_FLOATS * 4 * n, 256);
         }
+        // the forward blend -> the backward blend: per instance and quadrant, the eight half-row bits (bit 2r + h, gs2d_cull.h) of
+        // the 4x2 pixel blocks in which some pixel COMPOSITED the splat (one byte per quadrant): what the backward's queues are
+        // built from.  Last, so that every older array keeps its offset.
+        const size_t contrib = o; o = gs2d_align_up(o + 4 * n, 256);
         if (out) {
             out->point_list = point_list; out->hits = hits; out->hits4 = hits4; out->keys = keys; out->hist = hist;
-            out->hist_elems = hist_elems; out->det_inv = det_inv; out->det_slots = det_slots;
+            out->hist_elems = hist_elems; out->det_inv = det_inv; out->det_slots = det_slots; out->contrib = contrib;
         }
         return o;
     };
@@ -309,25 +313,27 @@ struct BlendFwdFrame {
     const uint2* ranges; uint32_t* point_list; const float4* rec;
     float* out_color; float* out_others; float* pix_state;
     uint8_t* hits; uint8_t* hits4;  // written by phase 0 (cull bits, gs2d_cull.h)
+    uint8_t* contrib;               // cleared by phase 0, written by the blend loop: the half-rows that composited each instance
     float4* zero;                   // the backward's gradient accumulator, cleared with the kernel's idle store slots
     uint64_t* keys; uint64_t* keys_alt; uint32_t* vals_alt;  // sort_cap > 0: the binned (depth, id) pairs of the tile lists + scratch
-    DevBin dev;                     // dev.base != nullptr: point_list, hits, hits4, keys, keys_alt, vals_alt are derived from it
+    DevBin dev;                     // dev.base != nullptr: point_list, hits, hits4, contrib, keys, keys_alt, vals_alt are derived from it
                                     // in the kernel (the host did not know num_rendered when it launched)
 };
 struct BlendFwdBatch { BlendFwdFrame f[GS2D_MAX_BATCH]; };
 struct BlendBwdFrame {
-    const uint2* ranges; const uint32_t* point_list; const float4* rec; const float* pix_state; const uint8_t* hits;
+    const uint2* ranges; const uint32_t* point_list; const float4* rec; const float* pix_state;
+    const uint8_t* contrib;  // the forward's record of who composited what: eight half-row bits per (instance, quadrant), bit 2r + h;
+                             // the four-queue kernels OR the pairs into row bits, the eight-queue pose-only kernel takes the byte as it is
     const float* dL_dpix; const float* dL_dothers; float* grad_rec;
     float* det_slots;  // != nullptr selects the deterministic variant (single frame only): no atomics, per-(instance, quadrant)
                        // partial records (GS2D_GRAD_FLOATS floats each, R * 4 of them, zero-initialised by the caller)
-    const uint16_t* hits16;  // the forward's sixteen group bits per (instance, quadrant): the eight-queue pose-only kernel derives
-                             // its half-row bits from them (the other kernels read `hits`, the forward's four row bits)
     float* dense_m2d;  // != nullptr selects the POSE-ONLY variant (single frame, non-deterministic): grad_rec is then used as a
                        // dense float4[P] (dT[2], dT[5], dT[8], -) and dense_m2d as float2[P] dL_dmean2D.xy (both zero on entry)
 };
 struct BlendBwdBatch { BlendBwdFrame f[GS2D_MAX_BATCH]; };
 // Writes hits (u16[4 * i + q] = the 2x2 pixel groups of quadrant q that instance i of the sorted list can touch, see
-// gs2d_cull.h) for every instance, then blends.  Also clears zero_n float4 at `zero` (the backward's gradient accumulator)
+// gs2d_cull.h) for every instance, then blends, and leaves in contrib (u8[4 * i + q]) the half-rows of quadrant q in which some
+// pixel composited instance i.  Also clears zero_n float4 at `zero` (the backward's gradient accumulator)
 // with its idle store slots.
 // sort_cap > 0 (GS2D_FUSED_SORT_CAP: pair sort, GS2D_FUSED_SORT_CAP_IDX: index sort): every workgroup first sorts its tile's list by depth (the per-tile depth sort as phase
 // -1, lists longer than sort_cap through global scratch), write_keys as in launch_tile_depth_sort

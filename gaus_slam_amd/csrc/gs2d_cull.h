@@ -110,26 +110,16 @@ __device__ __forceinline__ uint32_t rows_from_groups(uint32_t g16)
 {
     return ((g16 & 0x0033u) ? 1u : 0u) | ((g16 & 0x00CCu) ? 2u : 0u) | ((g16 & 0x3300u) ? 4u : 0u) | ((g16 & 0xCC00u) ? 8u : 0u);
 }
-// EXPERIMENT builds with eight backward queues per wave (-DGS2D_BWD_GROUPS=8 / -DGS2D_BWD_POSE_GROUPS=8, see gs2d_blend.hip and
-// profiles/bwd_queue_ab_r04.txt) store eight HALF-ROW bits per quadrant instead: from its sixteen group bits (bit 4 gy + gx).  The backward's 4x4 sub-block r = 2 ry + rx
-// (one per 16-lane DPP row) covers group columns 2rx, 2rx+1 and group rows 2ry, 2ry+1; its half h (4x2 pixels, the 8 lanes of
-// half a DPP row) is group row 2ry + h.  Bit 2r + h.  The four ROW bits of the 4-queue backward are the ORs of the pairs
-// (rows_from_halfrows).
-__device__ __forceinline__ uint32_t halfrows_from_groups(uint32_t g16)
+// Eight HALF-ROW bits per quadrant: the backward's 4x4 sub-block r = 2 ry + rx (one per 16-lane DPP row) covers group columns
+// 2rx, 2rx+1 and group rows 2ry, 2ry+1 (group bit 4 gy + gx); its half h (4x2 pixels, the 8 lanes of half a DPP row) is group
+// row 2ry + h.  Bit 2r + h.  The forward's blend loop records in this form which half-rows composited a splat (contrib); the
+// four ROW bits of the four-queue backward are the ORs of the pairs (rows_from_halfrows).
+// The half-row bit (2 r + h) of ONE group g = 4 gy + gx of a quadrant: what a forward wave's quad ORs into the contribution
+// byte of a splat one of its pixels composites (blend_fwd_kernel)
+__device__ __forceinline__ uint32_t halfrow_bit_of_group(int g)
 {
-    return ((g16 & 0x0003u) ? 0x01u : 0u) | ((g16 & 0x0030u) ? 0x02u : 0u) | ((g16 & 0x000Cu) ? 0x04u : 0u) | ((g16 & 0x00C0u) ? 0x08u : 0u) |
-           ((g16 & 0x0300u) ? 0x10u : 0u) | ((g16 & 0x3000u) ? 0x20u : 0u) | ((g16 & 0x0C00u) ? 0x40u : 0u) | ((g16 & 0xC000u) ? 0x80u : 0u);
-}
-// The same eight bits by bit tricks (13 operations instead of ~24): OR the adjacent bit pairs, compress the eight pair bits
-// (pair j = 4 ry + 2 h + rx) to a byte, swap the two middle positions of each nibble (-> bit 4 ry + 2 rx + h = 2 r + h).
-// Used by the eight-queue pose-only backward, which derives its half-row bits from the forward's group bits itself.
-__device__ __forceinline__ uint32_t halfrows_from_groups_fast(uint32_t g16)
-{
-    uint32_t x = (g16 | (g16 >> 1)) & 0x5555u;
-    x = (x | (x >> 1)) & 0x3333u;
-    x = (x | (x >> 2)) & 0x0F0Fu;
-    x = (x | (x >> 4)) & 0x00FFu;
-    return (x & 0x99u) | ((x & 0x22u) << 1) | ((x & 0x44u) >> 1);
+    const int gx = g & 3, gy = g >> 2;
+    return 1u << (4 * (gy >> 1) + 2 * (gx >> 1) + (gy & 1));
 }
 __device__ __forceinline__ uint32_t rows_from_halfrows(uint32_t h8)
 {
@@ -142,11 +132,11 @@ __device__ __forceinline__ uint32_t rows_from_halfrows(uint32_t h8)
 #endif
 // The tile's sorted segment walked by 256 threads, thread t takes instances t, t+256, ...; the two dependent gathers of
 // the NEXT instance (id, then 52 bytes of its record) are issued before the ~700 instructions of the current one, so only
-// a wave's first gather is exposed.  hits[i] = the 64 group bits of instance i (16 bits per quadrant).  (Tried and dropped: 1024-thread workgroups, -25 %; a flat one-instance-per-thread grid fed by
+// a wave's first gather is exposed.  hits[i] = the 64 group bits of instance i (16 bits per quadrant); contrib[i] is cleared.  (Tried and dropped: 1024-thread workgroups, -25 %; a flat one-instance-per-thread grid fed by
 // per-instance tile ids from the depth sort, -30 %: every wave then pays both gather latencies for one instance.)
 __device__ __forceinline__ void cull_tile_list(const uint2 range, float tx0, float ty0, const uint32_t* __restrict__ point_list,
                                                const float4* __restrict__ rec, uint64_t* __restrict__ hits,
-                                               uint32_t* __restrict__ hits4)
+                                               uint32_t* __restrict__ hits4, uint32_t* __restrict__ contrib)
 {
     uint32_t i = range.x + threadIdx.x;
     if (i >= range.y) return;
@@ -165,13 +155,9 @@ __device__ __forceinline__ void cull_tile_list(const uint2 range, float tx0, flo
         const float nrho = reinterpret_cast<const float*>(np)[18];
         const uint64_t m64 = splat_touch_mask64(r0, r1, r2, rho_max, tx0, ty0);
         hits[i] = m64;
-#if GS2D_HALFROW_BITS
-        hits4[i] = halfrows_from_groups((uint32_t)m64 & 0xFFFFu) | (halfrows_from_groups((uint32_t)(m64 >> 16) & 0xFFFFu) << 8) |
-                   (halfrows_from_groups((uint32_t)(m64 >> 32) & 0xFFFFu) << 16) | (halfrows_from_groups((uint32_t)(m64 >> 48)) << 24);
-#else
         hits4[i] = rows_from_groups((uint32_t)m64 & 0xFFFFu) | (rows_from_groups((uint32_t)(m64 >> 16) & 0xFFFFu) << 8) |
                    (rows_from_groups((uint32_t)(m64 >> 32) & 0xFFFFu) << 16) | (rows_from_groups((uint32_t)(m64 >> 48)) << 24);
-#endif
+        contrib[i] = 0u;  // the four quadrants' contribution bytes: the blend loop stores the bytes of the splats it reaches
         i += GS2D_CULL_T;
         if (i >= range.y) break;
         r0 = n0; r1 = n1; r2 = n2; rho_max = nrho; id_next = id_next2;

@@ -325,6 +325,11 @@ size_t gs2d_binning_bytes(int R);
  */
 void gs2d_geometry_layout(int P, size_t offsets[5]);
 void gs2d_binning_layout(int R, size_t offsets[2]);
+/* Byte offset, inside the binning chunk of a forward with num_rendered = R in the CURRENT mode (gs2d_set_deterministic), of
+ * contrib u8[R][4]: for instance i of the sorted list and quadrant q of its tile (q = (y/8)*2 + (x/8)), eight bits that say in
+ * which 4x2 pixel blocks of the quadrant some pixel composited the splat in the forward; bit 2*r + h = the 4x4 sub-block
+ * r = (y%8/4)*2 + (x%8/4), its upper (h = 0) or lower (h = 1) two pixel rows.  The backward builds its queues from it. */
+size_t gs2d_binning_contrib_offset(int R);
 void gs2d_image_layout(int width, int height, size_t offsets[2]);
 
 /* Optional per-stage device timing with hipEvents recorded on the launch stream (bench.py's roofline leg).
