@@ -1,14 +1,38 @@
-"""Host helpers shared by everything above the two C ABIs (include/gs2d_rasterizer.h, include/gs2d_map.h, include/gs2d_pose.h,
-include/gs2d_eval.h, include/gs2d_tsdf.h, include/gs2d_recon.h):
-device pointers, torch's current stream, the allocator callback the libraries ask for scratch memory through, and the ONE
-sequence every library call runs (`call`).  Imports torch and ctypes only, nothing from this package: _lib.py and _map_lib.py
-bind a library each and sit on top of this module, the operator modules on top of those."""
+"""Host helpers shared by everything above the C ABIs (the headers under include/): the ONE way a binding loads its library and
+applies its table of prototypes (`load`), the source hash inside a build info (`source_hash_of`), device pointers, torch's
+current stream, the allocator callback the libraries ask for scratch memory through, and the ONE sequence every library call
+runs (`call`).  Imports torch and ctypes only, nothing from this package: the nine bindings (_lib.py, _map_lib.py, ...) hold a
+table each and sit on top of this module, the operator modules on top of those."""
 import ctypes as C
 import itertools
+import os
 
-import torch
+import torch  # before any library is loaded: see load()
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)  # gs2d_alloc_fn
+
+
+def load(path, abi):
+    """The HIP library at `path` with every prototype of `abi`, {header: {entry point: (restype, argtypes)}}, applied.  A missing
+    library is an error: this package has no CPU fallback."""
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"gaus_slam_amd: HIP library {path} is missing. Build it with `python -m gaus_slam_amd.build` "
+            "(needs hipcc); this package has no CPU fallback.")
+    # torch first: its wheel bundles its own HIP runtime, and a process must end up with ONE libamdhip64.  Loading a
+    # library before torch pulls in /opt/rocm's copy as a second runtime, which then reports "no ROCm-capable device".
+    import torch  # noqa: F401  (bound at the top of this module already: kept here, where the order matters)
+    L = C.CDLL(path)
+    for group in abi.values():
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
+def source_hash_of(build_info_text):
+    """The source hash a library's build info ends with ("unknown" for a library not built by gaus_slam_amd/build.py)."""
+    return build_info_text.rsplit(" src ", 1)[1] if " src " in build_info_text else "unknown"
 
 
 def ptr(t):

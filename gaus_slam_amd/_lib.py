@@ -1,19 +1,17 @@
-"""ctypes binding of the C ABI (include/gs2d_rasterizer.h).  Fails loudly when the HIP library is missing:
-there is no CPU fallback anywhere in this package."""
+"""ctypes binding of the C ABI of libgs2d_hip.so (include/gs2d_rasterizer.h): the rasterizer, the fused loss and Adam, the kNN.
+ABI below is the one table of prototypes, of the shape of _map_lib.ABI; lib() applies it and tests/test_host.py compares it, the
+two structs and the constants with the header.  Fails loudly when the HIP library is missing: there is no CPU fallback anywhere
+in this package."""
 import ctypes as C
-import os
 
 from . import _host, build as _build
 
-ALLOC_FN = _host.ALLOC_FN  # gs2d_alloc_fn: one type object, so the allocator callback _host creates matches argtypes below
+ALLOC_FN = _host.ALLOC_FN  # gs2d_alloc_fn: one type object, so the allocator callback _host creates matches the argtypes below
 
-EXPORTS = ["gs2d_forward", "gs2d_backward", "gs2d_forward_posed", "gs2d_backward_posed", "gs2d_mark_visible", "sknn_dist2", "gs2d_geometry_bytes",
-           "gs2d_image_bytes", "gs2d_binning_bytes", "gs2d_geometry_layout", "gs2d_binning_layout",
-           "gs2d_image_layout", "gs2d_last_error", "gs2d_build_info", "gs2d_stage_timing_enable",
-           "gs2d_stage_timing_read", "gs2d_slam_loss", "gs2d_adam_step", "gs2d_pose_quat", "gs2d_backward_staged", "gs2d_set_deterministic",
-           "gs2d_get_deterministic", "gs2d_set_reference_binning", "gs2d_get_reference_binning", "gs2d_set_launch_ahead", "gs2d_get_launch_ahead", "gs2d_forward_batch",
-           "gs2d_backward_batch", "gs2d_stage_timing_read_abs", "gs2d_binning_contrib_offset"]
 MAX_FRAMES = 8  # GS2D_MAX_FRAMES
+BWD_BLEND, BWD_PREPROCESS, BWD_POSE_4X4 = 1, 2, 4  # GS2D_BWD_*: the bits of gs2d_backward_staged's `stages`
+LOSS_WS_DOUBLES = 2560  # GS2D_LOSS_WS_DOUBLES
+ADAM_MAX_GROUPS = 8  # GS2D_ADAM_MAX_GROUPS
 
 
 class FrameIO(C.Structure):
@@ -34,73 +32,67 @@ class FrameGrad(C.Structure):
                 ("dL_drot", C.c_void_p)]
 
 
+_vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
+# gs2d_forward without its stream: three (alloc, user) pairs, P D M, background, width height, means3D shs colors_precomp opacities
+# scales, scale_modifier, rotations transMat_precomp viewmatrix projmatrix cam_pos, tan_fovx tan_fovy prefiltered, out_color
+# out_others radii, use_sa debug
+_fwd = [ALLOC_FN, _vp] * 3 + [_i, _i, _i, _vp, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 5 + [_f, _f, _i] + [_vp] * 3 + [_i, _i]
+# gs2d_backward without its stream: P D M R, background, width height, means3D shs colors_precomp scales, scale_modifier, rotations
+# transMat_precomp viewmatrix projmatrix campos, tan_fovx tan_fovy, radii, three buffers, dL_dpix dL_depths, nine dL_* outputs,
+# use_sa debug
+_bwd = [_i] * 4 + [_vp, _i, _i] + [_vp] * 4 + [_f] + [_vp] * 5 + [_f, _f] + [_vp] * 15 + [_i, _i]
+# header -> {entry point: (restype, argtypes)}, in the order of the declarations
+ABI = {
+    "gs2d_rasterizer.h": {
+        "gs2d_forward": (_i, _fwd + [_vp]),
+        "gs2d_backward": (_i, _bwd + [_vp]),
+        "gs2d_pose_quat": (_i, [_vp, _vp, _vp]),
+        "gs2d_forward_posed": (_i, _fwd + [_vp, _vp, _vp]),  # .., pose_Rt, pose_quat, stream
+        "gs2d_backward_posed": (_i, _bwd + [_vp] * 4),  # .., pose_Rt, pose_quat, dL_dpose, stream
+        "gs2d_backward_staged": (_i, [_i, _i, _i] + _bwd + [_vp] * 4),  # stages, g_begin, g_end, then gs2d_backward_posed's
+        # K, frames, P D M, background, width height, means3D shs colors_precomp opacities scales, scale_modifier, rotations
+        # transMat_precomp, use_sa debug, num_rendered (host)
+        "gs2d_forward_batch": (_i, [_i, C.POINTER(FrameIO), _i, _i, _i, _vp, _i, _i] + [_vp] * 5 + [_f, _vp, _vp, _i, _i, C.POINTER(C.c_int), _vp]),
+        # K, frames, accumulate, P D M, background, width height, means3D shs colors_precomp scales, scale_modifier, rotations
+        # transMat_precomp, use_sa debug
+        "gs2d_backward_batch": (_i, [_i, C.POINTER(FrameGrad), _i, _i, _i, _i, _vp, _i, _i] + [_vp] * 4 + [_f, _vp, _vp, _i, _i, _vp]),
+        "gs2d_set_deterministic": (None, [_i]),
+        "gs2d_get_deterministic": (_i, []),
+        "gs2d_set_reference_binning": (None, [_i]),
+        "gs2d_set_launch_ahead": (None, [_i]),
+        "gs2d_get_launch_ahead": (_i, []),
+        "gs2d_get_reference_binning": (_i, []),
+        "gs2d_mark_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+        "sknn_dist2": (_i, [_i, _vp, _vp, ALLOC_FN, _vp, _vp]),  # N, points, out, ws_alloc, ws_user
+        # mode, width height, color allmap gt_color_hwc gt_depth, w_color w_depth w_dist silmask_th edge_thres, use_edge_growth
+        # use_weight_norm, eps depth_near depth_far, workspace loss_out dL_dcolor dL_dallmap upstream
+        "gs2d_slam_loss": (_i, [_i, _i, _i] + [_vp] * 4 + [_f] * 5 + [_i, _i, _f, _f, _f] + [_vp] * 6),
+        # n_groups, group_end group_lr (host), beta1 beta2, eps, step, n, param grad exp_avg exp_avg_sq
+        "gs2d_adam_step": (_i, [_i, _vp, _vp, _d, _d, _f, _i, C.c_ulonglong] + [_vp] * 5),
+        "gs2d_geometry_bytes": (_sz, [_i]),
+        "gs2d_image_bytes": (_sz, [_i, _i]),
+        "gs2d_binning_bytes": (_sz, [_i]),
+        "gs2d_geometry_layout": (None, [_i, C.POINTER(_sz)]),
+        "gs2d_binning_layout": (None, [_i, C.POINTER(_sz)]),
+        "gs2d_binning_contrib_offset": (_sz, [_i]),
+        "gs2d_image_layout": (None, [_i, _i, C.POINTER(_sz)]),
+        "gs2d_stage_timing_enable": (None, [_i]),
+        "gs2d_stage_timing_read": (_i, [C.POINTER(_f)]),
+        "gs2d_stage_timing_read_abs": (_i, [C.POINTER(_f)]),
+        "gs2d_last_error": (C.c_char_p, []),
+        "gs2d_build_info": (C.c_char_p, []),
+    },
+}
+EXPORTS = list(ABI["gs2d_rasterizer.h"])
+
 _lib = None
 
 
 def lib():
     global _lib
-    if _lib is not None:
-        return _lib
-    path = _build.LIB_PATH
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"gaus_slam_amd: HIP library {path} is missing. Build it with `python -m gaus_slam_amd.build` "
-            "(needs hipcc); this package has no CPU fallback.")
-    # torch first: its wheel bundles its own HIP runtime, and a process must end up with ONE libamdhip64.  Loading this
-    # library before torch pulls in /opt/rocm's copy as a second runtime, which then reports "no ROCm-capable device".
-    import torch  # noqa: F401
-    L = C.CDLL(path)
-    vp, i, f, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    L.gs2d_forward.restype = i
-    L.gs2d_forward.argtypes = [ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp, i, i, i, vp, i, i, vp, vp, vp, vp, vp, f, vp, vp,
-                               vp, vp, vp, f, f, i, vp, vp, vp, i, i, vp]
-    L.gs2d_backward.restype = i
-    L.gs2d_backward.argtypes = [i, i, i, i, vp, i, i, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp, vp,
-                                vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp]
-    L.gs2d_forward_posed.restype = i
-    L.gs2d_forward_posed.argtypes = L.gs2d_forward.argtypes[:-1] + [vp, vp, vp]
-    L.gs2d_backward_posed.restype = i
-    L.gs2d_backward_posed.argtypes = L.gs2d_backward.argtypes[:-1] + [vp, vp, vp, vp]
-    L.gs2d_backward_staged.restype = i
-    L.gs2d_backward_staged.argtypes = [i, i, i] + L.gs2d_backward_posed.argtypes
-    L.gs2d_forward_batch.restype = i
-    L.gs2d_forward_batch.argtypes = [i, C.POINTER(FrameIO), i, i, i, vp, i, i, vp, vp, vp, vp, vp, f, vp, vp, i, i,
-                                     C.POINTER(C.c_int), vp]
-    L.gs2d_backward_batch.restype = i
-    L.gs2d_backward_batch.argtypes = [i, C.POINTER(FrameGrad), i, i, i, i, vp, i, i, vp, vp, vp, vp, f, vp, vp, i, i, vp]
-    L.gs2d_pose_quat.restype = i
-    L.gs2d_pose_quat.argtypes = [vp, vp, vp]
-    L.gs2d_mark_visible.restype = i
-    L.gs2d_mark_visible.argtypes = [i, vp, vp, vp, vp, vp]
-    L.sknn_dist2.restype = i
-    L.sknn_dist2.argtypes = [i, vp, vp, ALLOC_FN, vp, vp]
-    for n in ("gs2d_geometry_bytes", "gs2d_binning_bytes", "gs2d_binning_contrib_offset"):
-        getattr(L, n).restype = sz
-        getattr(L, n).argtypes = [i]
-    L.gs2d_image_bytes.restype = sz
-    L.gs2d_image_bytes.argtypes = [i, i]
-    L.gs2d_geometry_layout.argtypes = [i, C.POINTER(sz)]
-    L.gs2d_binning_layout.argtypes = [i, C.POINTER(sz)]
-    L.gs2d_image_layout.argtypes = [i, i, C.POINTER(sz)]
-    L.gs2d_slam_loss.restype = i
-    L.gs2d_slam_loss.argtypes = [i, i, i, vp, vp, vp, vp, f, f, f, f, f, i, i, f, f, f, vp, vp, vp, vp, vp, vp]
-    L.gs2d_adam_step.restype = i
-    L.gs2d_adam_step.argtypes = [i, vp, vp, C.c_double, C.c_double, f, i, C.c_ulonglong, vp, vp, vp, vp, vp]
-    L.gs2d_set_deterministic.argtypes = [i]
-    L.gs2d_get_deterministic.restype = i
-    L.gs2d_set_reference_binning.argtypes = [i]
-    L.gs2d_set_launch_ahead.argtypes = [i]
-    L.gs2d_get_launch_ahead.restype = i
-    L.gs2d_get_reference_binning.restype = i
-    L.gs2d_stage_timing_enable.argtypes = [i]
-    L.gs2d_stage_timing_read.restype = i
-    L.gs2d_stage_timing_read.argtypes = [C.POINTER(C.c_float)]
-    L.gs2d_stage_timing_read_abs.restype = i
-    L.gs2d_stage_timing_read_abs.argtypes = [C.POINTER(C.c_float)]
-    L.gs2d_last_error.restype = C.c_char_p
-    L.gs2d_build_info.restype = C.c_char_p
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _host.load(_build.LIB_PATH, ABI)
+    return _lib
 
 
 def last_error():
@@ -120,5 +112,4 @@ def build_info():
 
 def lib_source_hash():
     """The source hash compiled into the loaded library ("unknown" for a library not built by gaus_slam_amd/build.py)."""
-    info = build_info()
-    return info.rsplit(" src ", 1)[1] if " src " in info else "unknown"
+    return _host.source_hash_of(build_info())

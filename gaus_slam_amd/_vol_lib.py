@@ -2,7 +2,6 @@
 table of prototypes, of the shape of _loss_lib.ABI; lib() applies it and tests/test_vol_host.py compares it with the header.  Like
 the other bindings it fails loudly when the library is missing: there is no CPU fallback."""
 import ctypes as C
-import os
 
 from . import _host, build as _build
 
@@ -44,21 +43,9 @@ _lib = None
 
 def lib():
     global _lib
-    if _lib is not None:
-        return _lib
-    path = _build.VOL_LIB_PATH
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"gaus_slam_amd: HIP library {path} is missing. Build it with `python -m gaus_slam_amd.build` "
-            "(needs hipcc); this package has no CPU fallback.")
-    import torch  # noqa: F401  (first, so that the process ends up with ONE HIP runtime: see _lib.lib)
-    L = C.CDLL(path)
-    for group in ABI.values():
-        for name, (restype, argtypes) in group.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _host.load(_build.VOL_LIB_PATH, ABI)
+    return _lib
 
 
 def last_error():
@@ -77,5 +64,4 @@ def build_info():
 
 
 def lib_source_hash():
-    info = build_info()
-    return info.rsplit(" src ", 1)[1] if " src " in info else "unknown"
+    return _host.source_hash_of(build_info())

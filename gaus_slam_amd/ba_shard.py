@@ -15,6 +15,8 @@ from collections import OrderedDict
 import torch
 import torch.distributed as dist
 
+from . import _lib  # the binding's constants: importing it loads no library
+
 # name -> floats per Gaussian, in bucket order
 BUCKET_FIELDS = OrderedDict([("means3D", 3), ("opacities", 1), ("scales", 2), ("rotations", 4), ("colors", 3)])
 BUCKET_FLOATS = sum(BUCKET_FIELDS.values())  # 13
@@ -89,7 +91,7 @@ class GradBucket:
         return self.flat
 
 
-MAX_BATCH_KEYFRAMES = 8  # GS2D_MAX_FRAMES
+MAX_BATCH_KEYFRAMES = _lib.MAX_FRAMES  # what one gs2d_forward_batch / gs2d_backward_batch takes
 _ENGINE_THREADS = os.environ.get("GS2D_AUTOGRAD_ENGINE_THREADS", "0") == "1"  # dev A/B switch, see local_backward
 
 

@@ -23,7 +23,7 @@ from . import _lib, _loss_lib
 from ._check import check_device, require
 from ._host import ptr
 
-_WS_DOUBLES = 2560  # GS2D_LOSS_WS_DOUBLES (include/gs2d_rasterizer.h)
+_WS_DOUBLES = _lib.LOSS_WS_DOUBLES
 
 
 def _call(cfg, W, H, color_, allmap_, gtc, gtd, ws, out, g_color, g_allmap, upstream, dev):

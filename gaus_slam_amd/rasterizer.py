@@ -19,8 +19,9 @@ from ._host import Chunk as _Chunk, chunks as _chunks, on_device as _on_device, 
 
 NUM_CHANNELS = 3
 # gs2d_backward_staged's `stages` (include/gs2d_rasterizer.h): GS2D_BWD_BLEND, GS2D_BWD_PREPROCESS, and both with
-# GS2D_BWD_POSE_4X4 (1|2|4: all sixteen floats of a [4,4] pose gradient are written)
-_BWD_BLEND, _BWD_PREPROCESS, _BWD_POSE_ONLY = 1, 2, 7
+# GS2D_BWD_POSE_4X4 (all sixteen floats of a [4,4] pose gradient are written)
+_BWD_BLEND, _BWD_PREPROCESS = _lib.BWD_BLEND, _lib.BWD_PREPROCESS
+_BWD_POSE_ONLY = _lib.BWD_BLEND | _lib.BWD_PREPROCESS | _lib.BWD_POSE_4X4
 
 
 def _check_cuda(t, name):

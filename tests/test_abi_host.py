@@ -1,8 +1,9 @@
 """CPU tests of the map library's host layer, once for all five C headers: the declared symbols are the bound and the exported
 ones, every prototype agrees with its row of _map_lib.ABI (count, kinds, return type), every integer #define has its Python
 mirror, build.py hashes and watches every header and source, and the modules above the binding import no more than they need.
-Nothing here launches a kernel.  The rasterizer library is not compared: its void entry points keep ctypes' default restype and
-gs2d_adam_step takes an `unsigned long long`, two special cases beyond the alloc callback and array parameters."""
+Nothing here launches a kernel.  The helpers below (_code, _prototypes, _matches, _defines) serve the other bindings' host tests
+too; the rasterizer library is compared by tests/test_host.py, for which they know the alloc callback, `unsigned long long`, a
+`void` return type and the one entry point without the gs2d_ prefix."""
 import ctypes as C
 import os
 import re
@@ -44,9 +45,9 @@ def _code(header):
     return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
 
 
-def _prototypes(header):
-    """{name: (return type, [parameter declarations])} of every gs2d_* function the header declares."""
-    found = re.findall(r"^[ \t]*((?:const[ \t]+)?\w+[ \t]*\*?)[ \t]*(gs2d_\w+)[ \t]*\(([^()]*)\)[ \t]*;", _code(header), flags=re.M)
+def _prototypes(header, names=r"gs2d_\w+"):
+    """{name: (return type, [parameter declarations])} of every function the header declares whose name matches `names`."""
+    found = re.findall(rf"^[ \t]*((?:const[ \t]+)?\w+[ \t]*\*?)[ \t]*({names})[ \t]*\(([^()]*)\)[ \t]*;", _code(header), flags=re.M)
     out = {}
     for ret, name, params in found:
         params = [" ".join(p.split()) for p in params.split(",")]
@@ -56,9 +57,10 @@ def _prototypes(header):
 
 
 def _scalar_types():
-    from gaus_slam_amd import _map_lib
+    from gaus_slam_amd import _host, _map_lib
     return {"int": C.c_int, "int32_t": C.c_int32, "float": C.c_float, "double": C.c_double, "uint32_t": C.c_uint32,
-            "uint64_t": C.c_uint64, "size_t": C.c_size_t, "gs2d_pose_cfg": _map_lib.PoseCfg}
+            "uint64_t": C.c_uint64, "size_t": C.c_size_t, "unsigned long long": C.c_ulonglong, "gs2d_pose_cfg": _map_lib.PoseCfg,
+            "gs2d_alloc_fn": _host.ALLOC_FN}  # the callback is a function pointer type of its own, not a plain pointer
 
 
 def _is_pointer(ctype):
@@ -71,7 +73,9 @@ def _matches(decl, ctype, is_return=False):
         return ctype is C.c_char_p if is_return else _is_pointer(ctype)
     words = [w for w in decl.split() if w != "const"]
     ctype_of = _scalar_types()
-    kind = words[0] if is_return else " ".join(words[:-1])
+    kind = " ".join(words) if is_return else " ".join(words[:-1])
+    if is_return and kind == "void":
+        return ctype is None
     return kind in ctype_of and ctype is ctype_of[kind]
 
 
@@ -128,6 +132,18 @@ def test_the_prototype_comparison_tells_the_kinds_apart():
     protos = _prototypes("gs2d_tsdf.h")
     assert len(protos["gs2d_tsdf_integrate"][1]) == 30 and protos["gs2d_tsdf_tet_case"] == ("uint64_t", ["int tet", "int mask"])
     assert _prototypes("gs2d_map.h")["gs2d_map_last_error"] == ("const char*", [])
+    # what the rasterizer header adds: the alloc callback, `unsigned long long`, `void` returns, a name without the gs2d_ prefix
+    from gaus_slam_amd import _host
+    assert _matches("gs2d_alloc_fn geometry_alloc", _host.ALLOC_FN) and not _matches("gs2d_alloc_fn geometry_alloc", vp)
+    assert _matches("void* stream", vp) and not _matches("void* stream", _host.ALLOC_FN)
+    assert _matches("unsigned long long n", C.c_ulonglong) and not _matches("unsigned long long n", i)
+    assert _matches("const unsigned long long* group_end", vp)
+    assert _matches("void", None, True) and not _matches("void", i, True) and not _matches("int", None, True)
+    assert not _matches("size_t", None, True) and _matches("size_t", C.c_size_t, True)
+    protos = _prototypes("gs2d_rasterizer.h", r"(?:gs2d|sknn)_\w+")
+    assert len(protos) == 30 and "sknn_dist2" in protos and "sknn_dist2" not in _prototypes("gs2d_rasterizer.h")
+    assert len(protos["gs2d_backward_staged"][1]) == 43 and len(protos["gs2d_forward_posed"][1]) == 34
+    assert protos["gs2d_set_deterministic"] == ("void", ["int on"]) and protos["gs2d_get_deterministic"] == ("int", [])
 
 
 # --------------------------------------------------------------------------------------------------------------------- constants

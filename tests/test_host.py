@@ -1,5 +1,6 @@
 """CPU tests of the host side: the C-ABI library loads and exports every symbol include/gs2d_rasterizer.h declares
-(no compute calls without a GPU), the operator mirror validates arguments like the reference, and the product
+(no compute calls without a GPU), every row of _lib.ABI, both frame structs and every integer constant agree with that header
+(with the helpers of tests/test_abi_host.py), the operator mirror validates arguments like the reference, and the product
 never falls back to the CPU."""
 import ctypes as C
 import os
@@ -7,6 +8,8 @@ import re
 
 import pytest
 import torch
+
+from tests import test_abi_host as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,6 +30,91 @@ def test_library_exports_every_declared_symbol(hiplib):
         assert hasattr(hiplib, n), n
     from gaus_slam_amd import _lib
     assert set(_lib.EXPORTS) == names
+
+
+# -------------------------------------------------------------------- the binding table against include/gs2d_rasterizer.h
+HEADER = "gs2d_rasterizer.h"
+EVERY_NAME = r"(?:gs2d|sknn)_\w+"  # sknn_dist2 is the one entry point without the gs2d_ prefix
+# What the header declares, written out in its order: a symbol dropped from header and binding alike still fails here.
+NAMES = ["gs2d_forward", "gs2d_backward", "gs2d_pose_quat", "gs2d_forward_posed", "gs2d_backward_posed", "gs2d_backward_staged",
+         "gs2d_forward_batch", "gs2d_backward_batch", "gs2d_set_deterministic", "gs2d_get_deterministic",
+         "gs2d_set_reference_binning", "gs2d_set_launch_ahead", "gs2d_get_launch_ahead", "gs2d_get_reference_binning",
+         "gs2d_mark_visible", "sknn_dist2", "gs2d_slam_loss", "gs2d_adam_step", "gs2d_geometry_bytes", "gs2d_image_bytes",
+         "gs2d_binning_bytes", "gs2d_geometry_layout", "gs2d_binning_layout", "gs2d_binning_contrib_offset", "gs2d_image_layout",
+         "gs2d_stage_timing_enable", "gs2d_stage_timing_read", "gs2d_stage_timing_read_abs", "gs2d_last_error", "gs2d_build_info"]
+
+
+def test_declared_symbols_are_the_bound_and_the_exported_ones(hiplib):
+    import shutil
+    import subprocess
+    from gaus_slam_amd import build, _lib
+    assert len(NAMES) == len(set(NAMES)) == 30
+    assert NAMES == list(abi._prototypes(HEADER, EVERY_NAME))  # the header's order
+    assert list(_lib.ABI) == [HEADER] and NAMES == list(_lib.ABI[HEADER]) == _lib.EXPORTS
+    for n in NAMES:
+        assert hasattr(hiplib, n), n
+    if shutil.which("nm") and not os.environ.get("GS2D_LIB_PATH"):  # the dynamic symbol table: nothing else carries the prefixes
+        nm = subprocess.run(["nm", "-D", "--defined-only", build.LIB_PATH], capture_output=True, text=True)
+        if nm.returncode == 0:
+            assert set(re.findall(r"\b((?:gs2d|sknn)_[a-z0-9_]+)\b", nm.stdout)) == set(NAMES)
+
+
+def test_prototypes_agree_with_the_binding_table(hiplib):
+    from gaus_slam_amd import _lib
+    protos = abi._prototypes(HEADER, EVERY_NAME)
+    assert set(protos) == set(_lib.ABI[HEADER])
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib.ABI[HEADER][name]
+        assert len(params) == len(argtypes), (name, len(params), len(argtypes))
+        for k, (decl, ctype) in enumerate(zip(params, argtypes)):
+            assert abi._matches(decl, ctype), (name, k, decl, ctype)
+        assert abi._matches(ret, restype, is_return=True), (name, ret, restype)
+        fn = getattr(hiplib, name)  # and lib() applied the table
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert "float scale_modifier" in protos["gs2d_backward_staged"][1] and "unsigned long long n" in protos["gs2d_adam_step"][1]
+    for name in ("gs2d_forward", "gs2d_backward_staged", "gs2d_forward_batch", "gs2d_slam_loss", "sknn_dist2"):
+        assert protos[name][1][-1] == "void* stream" and protos[name][0] == "int", name
+
+
+def _struct_fields(header, struct):
+    """[(name, declaration)] of the fields of `typedef struct <struct> {...}`; `float a, b;` gives two of them."""
+    body = re.search(rf"typedef\s+struct\s+{struct}\s*\{{(.*?)\}}\s*{struct}\s*;", abi._code(header), flags=re.S).group(1)
+    out = []
+    for decl in (" ".join(d.split()) for d in body.split(";")):
+        if not decl:
+            continue
+        first, *more = [p.strip() for p in decl.split(",")]
+        assert not more or "*" not in decl, decl  # `float* a, b` would need the declarator rules of C
+        kind = first.rsplit(" ", 1)[0]
+        for field in [first] + [f"{kind} {m}" for m in more]:
+            out.append((field.rsplit(" ", 1)[1], field))
+    return out
+
+
+def test_frame_structs_mirror_the_headers_field_by_field():
+    from gaus_slam_amd import _lib
+    for struct, mirror, n in (("gs2d_frame_io", _lib.FrameIO, 12), ("gs2d_frame_grad", _lib.FrameGrad, 21)):
+        fields = _struct_fields(HEADER, struct)
+        assert len(fields) == n == len(mirror._fields_), struct
+        assert [name for name, _ in fields] == [name for name, _ in mirror._fields_], struct  # names, in order
+        for (name, decl), (_, ctype) in zip(fields, mirror._fields_):
+            assert abi._matches(decl, ctype), (struct, decl, ctype)
+    assert ("tan_fovy", "float tan_fovy") in _struct_fields(HEADER, "gs2d_frame_grad")  # the comma was split
+    assert len(re.findall(r"typedef\s+struct", abi._code(HEADER))) == 2
+
+
+def test_every_integer_define_has_its_python_mirror():
+    from gaus_slam_amd import _lib, ba_shard, loss, rasterizer
+    defs = {name: value for name, (value, _) in abi._defines(HEADER).items()}
+    assert defs == {"GS2D_BWD_BLEND": 1, "GS2D_BWD_PREPROCESS": 2, "GS2D_BWD_POSE_4X4": 4, "GS2D_MAX_FRAMES": 8,
+                    "GS2D_LOSS_WS_DOUBLES": 2560, "GS2D_ADAM_MAX_GROUPS": 8}
+    for name, value in defs.items():
+        assert getattr(_lib, name[len("GS2D_"):]) == value, name
+    # and what the modules above the binding derive from them
+    assert (rasterizer._BWD_BLEND, rasterizer._BWD_PREPROCESS, rasterizer._BWD_POSE_ONLY) == (1, 2, 7)
+    assert rasterizer._BWD_POSE_ONLY == defs["GS2D_BWD_BLEND"] | defs["GS2D_BWD_PREPROCESS"] | defs["GS2D_BWD_POSE_4X4"]
+    assert loss._WS_DOUBLES == defs["GS2D_LOSS_WS_DOUBLES"] and ba_shard.MAX_BATCH_KEYFRAMES == defs["GS2D_MAX_FRAMES"]
+    assert len(ba_shard.BUCKET_FIELDS) <= defs["GS2D_ADAM_MAX_GROUPS"]  # optim.py's one group per bucket field
 
 
 def test_layout_queries_are_consistent(hiplib):
