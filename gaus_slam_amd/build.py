@@ -8,7 +8,9 @@ block-hashed TSDF volume (C ABI in include/gs2d_vol.h, sources in csrc_vol/), an
 (C ABI in include/gs2d_covis.h, sources in csrc_covis/), and the LPIPS library: the AlexNet trunk on the f32 MFMA and the metric's
 tail (C ABI in include/gs2d_lpips.h, sources in csrc_lpips/), and the frontend library: sensor-frame ingest, the frame-closing
 decision and batched camera set-up (C ABI in include/gs2d_front.h, sources in csrc_front/), and the ingest library: the sensor-frame
-ingest with separate colour and depth sizes and colour undistortion (C ABI in include/gs2d_ingest.h, sources in csrc_ingest/).
+ingest with separate colour and depth sizes and colour undistortion (C ABI in include/gs2d_ingest.h, sources in csrc_ingest/),
+and the view library: the saved images of a rendered view and its depth errors (C ABI in include/gs2d_view.h, sources in
+csrc_view/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -83,6 +85,13 @@ CSRC_INGEST = os.path.join(_HERE, "csrc_ingest")
 INGEST_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_ingest_hip.so")
 INGEST_SOURCES = ["gs2d_ingest.hip"]
 INGEST_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_ingest.h")]
+
+# The saved images of a view are a tenth library, for the same reason.  It includes nothing of csrc/ and restates the depth rule
+# and the fixed-order sums of csrc_map/.
+CSRC_VIEW = os.path.join(_HERE, "csrc_view")
+VIEW_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_view_hip.so")
+VIEW_SOURCES = ["gs2d_view.hip"]
+VIEW_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_view.h")]
 
 
 def _hash(directory, headers):
@@ -270,8 +279,24 @@ def build_ingest(force=False, verbose=False):
     return _compile(INGEST_LIB_PATH, [os.path.join(CSRC_INGEST, f) for f in INGEST_SOURCES], "GS2D_INGEST_SOURCE_HASH", ingest_source_hash(), verbose)
 
 
+def view_source_hash():
+    """source_hash() of the view library: every file under csrc_view/ plus VIEW_HEADERS (gs2d_view_build_info reports it)."""
+    return _hash(CSRC_VIEW, VIEW_HEADERS)
+
+
+def _view_stale():
+    deps = [os.path.join(CSRC_VIEW, f) for f in os.listdir(CSRC_VIEW)] + VIEW_HEADERS
+    return _is_stale(VIEW_LIB_PATH, view_source_hash(), deps)
+
+
+def build_view(force=False, verbose=False):
+    if not force and not _view_stale():
+        return VIEW_LIB_PATH
+    return _compile(VIEW_LIB_PATH, [os.path.join(CSRC_VIEW, f) for f in VIEW_SOURCES], "GS2D_VIEW_SOURCE_HASH", view_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the nine libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the ten libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
@@ -280,6 +305,7 @@ def build(force=False, verbose=False):
     build_lpips(force, verbose)
     build_front(force, verbose)
     build_ingest(force, verbose)
+    build_view(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -297,3 +323,4 @@ if __name__ == "__main__":
     print(LPIPS_LIB_PATH)
     print(FRONT_LIB_PATH)
     print(INGEST_LIB_PATH)
+    print(VIEW_LIB_PATH)

@@ -1,5 +1,5 @@
 """Readers of recorded RGB-D sequences, as sequences for slam.run_slam: plain Python on the CPU, written from the on-disk layouts
-of the reference's datasets (datasets/gradslam_datasets/{replica,tum,scannet}.py), not from its loaders.
+of the reference's datasets (datasets/gradslam_datasets/{replica,tum,scannet,scannetpp}.py), not from its loaders.
 
     seq = ReplicaSequence(basedir, "kitchen", camera)        # camera: the camera_params mapping of a camera.yaml
     seq = open_sequence(config["data"])                      # from a reference config's `data` section
@@ -18,6 +18,7 @@ Departures: the TUM pose list is read without its comment lines and nothing else
 line, which is a comment in every published sequence); ScanNetSequence(ignore_bad=True) drops the frames of the selected range
 whose pose is not finite (the reference accepts the flag and leaves such frames in)."""
 import glob
+import json
 import math
 import os
 import re
@@ -25,7 +26,7 @@ import re
 import numpy as np
 import torch
 
-KNOWN = ("replica", "tum", "scannet")
+KNOWN = ("replica", "tum", "scannet", "scannetpp")
 MAX_DT = 0.08  # seconds between a colour stamp and the depth / pose stamp associated with it (TUM)
 FRAME_RATE = 32  # successive TUM frames are more than 1 / FRAME_RATE seconds apart
 
@@ -94,7 +95,7 @@ def _rows(path):
 
 
 class RecordedSequence:
-    """What the three readers share: the camera, the frame selection and the decoding of one frame."""
+    """What the readers share: the camera, the frame selection and the decoding of one frame."""
 
     def __init__(self, camera, color_paths, depth_paths, poses, start=0, end=-1, stride=1):
         camera = camera.get("camera_params", camera)
@@ -215,7 +216,76 @@ class ScanNetSequence(RecordedSequence):
                 setattr(self, name, [getattr(self, name)[k] for k in good])
 
 
-READERS = {"replica": ReplicaSequence, "tum": TUMSequence, "scannet": ScanNetSequence}
+class ScanNetPPSequence(RecordedSequence):
+    """<basedir>/<sequence>/dslr: train_test_lists.json names the `train` and `test` images, in the order they are used (not the
+    natural one); nerfstudio/transforms_undistorted.json holds the camera (h, w, fl_x, fl_y, cx, cy) and, under `frames` for the
+    train and `test_frames` for the test images, one entry per image with file_path, transform_matrix (4x4) and is_bad.  Colour is
+    undistorted_images/<name>, depth undistorted_depths/<name with .JPG replaced by .png>, in millimetres (png_depth_scale 1000);
+    no camera file is needed.  The pose is P @ transform_matrix @ P.T with P = diag(1, -1, -1, 1), in float64.
+    use_train_split=False yields the FIRST TRAIN IMAGE first, never filtered by is_bad, then the test list: relative to that
+    anchor the held-out poses land in the frame of a map built from the train split.  ignore_bad drops the listed images whose
+    entry has is_bad true.  start / end / stride slice the resulting list, anchor included."""
+
+    def __init__(self, basedir, sequence, camera=None, start=0, end=-1, stride=1, ignore_bad=False, use_train_split=True):
+        folder = os.path.join(basedir, sequence, "dslr")
+        lists_path = os.path.join(folder, "train_test_lists.json")
+        meta_path = os.path.join(folder, "nerfstudio", "transforms_undistorted.json")
+        with open(lists_path) as fh:
+            lists = json.load(fh)
+        with open(meta_path) as fh:
+            meta = json.load(fh)
+
+        def key(mapping, name, path):
+            if not isinstance(mapping, dict) or name not in mapping:
+                raise ValueError(f"{path} lacks the key {name!r}")
+            return mapping[name]
+
+        train, test = list(key(lists, "train", lists_path)), list(key(lists, "test", lists_path))
+        cam = {"png_depth_scale": 1000.0}  # millimetres
+        for ours, theirs in (("image_height", "h"), ("image_width", "w"), ("fx", "fl_x"), ("fy", "fl_y"), ("cx", "cx"), ("cy", "cy")):
+            cam[ours] = key(meta, theirs, meta_path)
+        P = np.diag([1.0, -1.0, -1.0, 1.0])
+
+        def entries(group):
+            return {key(e, "file_path", f"{meta_path}: an entry of {group!r}"): e for e in key(meta, group, meta_path)}
+
+        def entry(table, group, name):
+            if name not in table:
+                raise ValueError(f"{meta_path}: {group!r} has no entry for the image {name!r} that {lists_path} lists")
+            return table[name]
+
+        def pose(e, group):
+            m = np.asarray(key(e, "transform_matrix", f"{meta_path}: an entry of {group!r}"), np.float64)
+            if m.shape != (4, 4):
+                raise ValueError(f"{meta_path}: the transform_matrix of {e.get('file_path')!r} is not 4x4")
+            return P @ m @ P.T
+
+        train_table = entries("frames")
+        names, poses = [], []
+        if use_train_split:
+            listed, table, group = train, train_table, "frames"
+        else:
+            listed, table, group = test, entries("test_frames"), "test_frames"
+            if not train:
+                raise ValueError(f"{lists_path}: the train list is empty, so there is no anchor frame")
+            names.append(train[0])
+            poses.append(pose(entry(train_table, "frames", train[0]), "frames"))
+        for name in listed:
+            e = entry(table, group, name)
+            if ignore_bad and key(e, "is_bad", f"{meta_path}: the entry of {name!r}"):
+                continue
+            names.append(name)
+            poses.append(pose(e, group))
+        if not names:
+            raise ValueError(f"{lists_path}: the selection holds no frame")
+        self.image_names = names
+        colors = [os.path.join(folder, "undistorted_images", n) for n in names]
+        depths = [os.path.join(folder, "undistorted_depths", n.replace(".JPG", ".png")) for n in names]
+        super().__init__(cam, colors, depths, poses, start, end, stride)
+        self.image_names = [names[k] for k in self.retained]
+
+
+READERS = {"replica": ReplicaSequence, "tum": TUMSequence, "scannet": ScanNetSequence, "scannetpp": ScanNetPPSequence}
 
 
 def working_size(data_cfg):
@@ -228,7 +298,7 @@ def working_size(data_cfg):
 def open_sequence(data_cfg):
     """A reader from the `data` section of a reference configuration: gradslam_data_cfg (the camera file, which also names the
     dataset; without it dataset_name of the section itself), basedir, sequence (its last path component), start, end, stride,
-    ignore_bad.  desired_image_width / height do not touch the reader: working_size() hands them to config['cameras']."""
+    ignore_bad and, for ScanNet++ (which needs no camera file), use_train_split.  desired_image_width / height do not touch the reader: working_size() hands them to config['cameras']."""
     if "gradslam_data_cfg" in data_cfg:
         cam = load_camera(data_cfg["gradslam_data_cfg"])
     else:
@@ -240,6 +310,8 @@ def open_sequence(data_cfg):
         if key not in data_cfg:
             raise ValueError(f"the data section lacks {key!r}")
     kw = dict(start=data_cfg.get("start", 0), end=data_cfg.get("end", -1), stride=data_cfg.get("stride", 1))
-    if name == "scannet":
+    if name in ("scannet", "scannetpp"):
         kw["ignore_bad"] = bool(data_cfg.get("ignore_bad", False))
+    if name == "scannetpp":
+        kw["use_train_split"] = bool(data_cfg.get("use_train_split", True))
     return READERS[name](str(data_cfg["basedir"]), os.path.basename(str(data_cfg["sequence"])), cam["camera_params"], **kw)

@@ -12,14 +12,20 @@ row per frame in a device tensor and reads the host once at the end.
 
     res = evaluate_map(params, frames, tsdf=vol, mesh_intrinsics=K)                # also fuses the renders into a tsdf.TSDFVolume
     res = evaluate_map(params, frames, lpips=lpips.LPIPS.from_files(alex, lin))    # also lpips, mean_lpips (eval.py:409-410)
+    res = evaluate_map(params, frames, dump_dir="eval")                            # also eval_final's saved images
+    res = evaluate_nvs(params, seq, (876, 584), out_dir="run/nvs_result")          # eval_nvs (eval.py:120-251) on held-out views
 
 LPIPS is gaus_slam_amd/lpips.py (include/gs2d_lpips.h): a model built from the two weight files a user of the reference has on
 disk; no weights ship here and none are fetched.  The published network's weights were never available to this project, so the
 agreement with torchmetrics on them is unverified: what is verified is the arithmetic on random weights and the loader's key
-mapping.  Not covered: the mesh metrics of utils/eval_mesh.py, and saving the rendered images.  The TSDF mesh itself is
-gaus_slam_amd/tsdf.py.
+mapping.  The saved images (the render, the colour-mapped depth and depth difference) are gaus_slam_amd/view_dump.py
+(include/gs2d_view.h): bytes made on the device, one copy per frame, PNGs written with Pillow.  Not covered: the mesh metrics
+of utils/eval_mesh.py.  The TSDF mesh itself is gaus_slam_amd/tsdf.py.
 
 No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError."""
+import json
+import os
+
 import numpy as np
 import torch
 
@@ -114,7 +120,7 @@ def _umeyama_rigid(x, y):
 
 
 def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2,
-                 clamp_color=False, tsdf=None, mesh_interval=1, mesh_extrinsics=None, mesh_intrinsics=None, lpips=None):
+                 clamp_color=False, tsdf=None, mesh_interval=1, mesh_extrinsics=None, mesh_intrinsics=None, lpips=None, dump_dir=None):
     """eval_final's loop over the frames.  params: the activated leaves render.render takes, a dict with means3D, opacities,
     scales, rotations and colors (or colors_precomp, or shs).  frames: a sequence of (settings, gt_color, gt_depth), the raster
     settings of each view (at its estimated pose) and its RGB-D frame.  Every view is rendered under torch.no_grad() with the
@@ -131,7 +137,11 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     lpips: an lpips.LPIPS model.  Every frame's render then also goes through lpips.frame (fourteen more launches per frame, no
     host read) into row k of a second device tensor, read at the end with the first: the result gains `lpips` (per frame),
     `mean_lpips` and `lpips_per_frame` (the whole [K, LPIPS_OUT_DOUBLES] array).  With lpips=None nothing changes: the same
-    launches and the same bits."""
+    launches and the same bits.
+    dump_dir: a directory.  Every frame's render then also goes through view_dump.frame_images in "final" mode (two more
+    launches and one copy of 9 H W bytes per frame) and is written as eval_final writes it (eval.py:357-376):
+    rendering/rgb/GauS_%04d.png, rendering/depth/GauS_%04d.png and rendering/diff/differ_%04d.png.  The result gains `view_per_frame`,
+    the [K, view_dump.OUT_DOUBLES] array.  With dump_dir=None nothing changes: the same launches and the same bits."""
     from . import render as _render
     require(len(frames) >= 1, "frames is empty")
     if tsdf is not None:
@@ -149,6 +159,7 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     ws = None
     lpips_rows = None if lpips is None else torch.empty((len(frames), LPIPS_OUT_DOUBLES), dtype=torch.float64, device=dev)
     lpips_ws = None
+    dump = None if dump_dir is None else _Dump(dump_dir, len(frames), dev, "differ_%04d.png")
     with torch.no_grad():
         means2D = torch.zeros_like(p["means3D"])
         for k, (settings, gt_color, gt_depth) in enumerate(frames):
@@ -163,6 +174,8 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
                 if lpips_ws is None or lpips_ws.numel() < lpips.ws_bytes(W, H):
                     lpips_ws = lpips.workspace(W, H)
                 lpips.frame(pkg["render_color"], gt_color, gt_depth, out=lpips_rows[k], ws=lpips_ws)
+            if dump is not None:
+                dump.frame(k, pkg, gt_depth, "final", use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
             if tsdf is not None and k % int(mesh_interval) == 0:
                 w2c = mesh_extrinsics[k] if mesh_extrinsics is not None else settings.viewmatrix.reshape(4, 4).t().contiguous()
                 tsdf.integrate_render(pkg["render_color"], pkg["allmap"], mesh_intrinsics, w2c, use_weight_norm=use_weight_norm,
@@ -176,6 +189,132 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
         res["lpips_per_frame"] = lpips_rows.cpu().numpy()
         res["lpips"] = res["lpips_per_frame"][:, LPIPS_VALUE].copy()
         res["mean_lpips"] = float(res["lpips"].mean())
+    if dump is not None:
+        res["view_per_frame"] = dump.rows.cpu().numpy()
     if est_w2cs is not None:
         res["ate_rmse"] = ate_rmse(est_w2cs, gt_w2cs)
+    return res
+
+
+class _Dump:
+    """The saved images of a loop over frames: view_dump.frame_images into row k of one device tensor and, with save=True, one
+    [3,H,W,3] device tensor whose 9 H W bytes go to one reused pinned buffer per frame; Pillow writes the three PNGs."""
+
+    def __init__(self, directory, n_frames, device, diff_name, save=True, tables=(None, None)):
+        from . import view_dump
+        self.view_dump, self.dir, self.dev, self.diff_name, self.save, self.tables = view_dump, directory, device, diff_name, save, tables
+        self.rows = torch.empty((n_frames, view_dump.OUT_DOUBLES), dtype=torch.float64, device=device)
+        self.images = self.host = self.ws = None
+        if save:
+            for sub in ("rgb", "depth", "diff"):
+                os.makedirs(os.path.join(directory, "rendering", sub), exist_ok=True)
+
+    def frame(self, k, pkg, gt_depth, mode, **kw):
+        from . import _view_lib
+        vd = self.view_dump
+        H, W = int(pkg["allmap"].shape[1]), int(pkg["allmap"].shape[2])
+        if self.ws is None or self.ws.numel() < _view_lib.lib().gs2d_view_ws_bytes(W, H):
+            self.ws = vd.workspace(W, H, self.dev)
+        if self.save and (self.images is None or tuple(self.images.shape) != (3, H, W, 3)):
+            self.images = torch.empty((3, H, W, 3), dtype=torch.uint8, device=self.dev)
+            self.host = torch.empty((3, H, W, 3), dtype=torch.uint8).pin_memory()
+        vd.frame_images(pkg["render_color"], pkg["allmap"], gt_depth, mode=mode, lut_depth=self.tables[0], lut_diff=self.tables[1],
+                        want=(self.save,) * 3, out=self.rows[k], images=self.images, ws=self.ws, **kw)
+        if self.save:
+            from PIL import Image
+            self.host.copy_(self.images, non_blocking=True)
+            torch.cuda.current_stream(self.dev).synchronize()  # the one wait of a saved frame: the bytes are on the host
+            arrays = self.host.numpy()
+            for plane, sub, name in ((vd.COLOR, "rgb", "GauS_%04d.png"), (vd.DEPTH, "depth", "GauS_%04d.png"), (vd.DIFF, "diff", self.diff_name)):
+                Image.fromarray(arrays[plane]).save(os.path.join(self.dir, "rendering", sub, name % k))
+
+
+NVS_KEYS = ("PSNR: ", "SSIM: ", "LPIPS: ", "Depth RMSE: ", "Depth L1: ")  # eval.py:231-237, verbatim
+
+
+def evaluate_nvs(params, sequence, size, *, intrinsics=None, use_sa=True, use_weight_norm=True, eps=1e-6, depth_near=1e-2, depth_far=1e2,
+                 lpips=None, out_dir=None, save_renders=True, lut_depth=None, lut_diff=None):
+    """eval_nvs's loop (eval.py:120-251) over held-out views.  params: the activated leaves, as for evaluate_map.  sequence: a
+    reader opened with use_train_split=False (datasets.ScanNetPPSequence), whose first frame is the anchor, the first train image:
+    every pose is taken relative to it (frontend_ops.compose), as run_slam does with its first frame, so the views land in the
+    frame of a map built from the train split.  The anchor is evaluated like every other frame, as in the reference.  size: the
+    working (W, H); intrinsics: (fx, fy, cx, cy) or a 3x3 at that size, None for the sequence's own, scaled.
+    Per frame: ingest / ingest_ex (chosen as run_slam does), the view is the inverse of the relative pose, with the raster
+    settings of ALL views from one frontend_ops.cameras launch; the render under torch.no_grad(); frame_metrics(clamp_color=True)
+    for PSNR and MS-SSIM; lpips.frame when a model is given; view_dump.frame_images in "nvs" mode for depth RMSE / L1 (of the
+    depth divided by alpha once more, eval.py:171) and the images.  The rows collect in device tensors that are read once at
+    the end.  With out_dir: psnr.txt, rmse.txt, l1.txt, ssim.txt, (lpips.txt) and nvs_result.json -- NVS_KEYS with the means,
+    "LPIPS: " null without a model, plus `build`, the stamps of the libraries used -- and, with save_renders,
+    rendering/{rgb,depth,diff}/GauS_%04d.png from one copy of 9 H W bytes per frame.  lut_depth, lut_diff: colour tables for
+    view_dump.frame_images, None for colormaps.JET / PLASMA.
+    Returns a dict: per-frame float64 arrays psnr, ms_ssim, depth_rmse, depth_l1 (lpips), their means mean_*, per_frame and
+    view_per_frame (the whole row arrays), and result (what nvs_result.json holds)."""
+    from . import _front_lib, _ingest_lib, _lib, _lpips_lib, _view_lib, frontend_ops as _ops, render as _render, view_dump
+    W, H = int(size[0]), int(size[1])
+    K = len(sequence)
+    require(K >= 1, "sequence is empty")
+    p = dict(params)
+    colors = p.pop("colors", None)
+    if colors is not None:
+        p["colors_precomp"] = colors
+    require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
+    dev = p["means3D"].device
+    W0, H0 = sequence.size
+    if intrinsics is None:
+        intrinsics = _ops.scaled_intrinsics(sequence.intrinsics, (W0, H0), (W, H))
+    distortion = getattr(sequence, "distortion", None)
+    extended = distortion is not None or tuple(getattr(sequence, "depth_size", None) or (W0, H0)) != (W0, H0)
+    poses = getattr(sequence, "poses", None)
+    if poses is None:
+        poses = [c2w for _, _, c2w in sequence]
+    c2ws = torch.stack([torch.as_tensor(np.asarray(m)).to(torch.float32) for m in poses]).to(dev).contiguous()
+    rel = _ops.compose(_ops.compose(c2ws[0].contiguous(), inv_a=True), c2ws, ia=[0] * K)  # relative_pose=True of the reference's datasets
+    settings = _ops.cameras(W, H, intrinsics, rel, inv_a=True, use_sa=use_sa)
+    rows = torch.empty((K, EVAL_OUT_DOUBLES), dtype=torch.float64, device=dev)
+    lpips_rows = None if lpips is None else torch.empty((K, LPIPS_OUT_DOUBLES), dtype=torch.float64, device=dev)
+    save = bool(save_renders) and out_dir is not None
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    dump = _Dump(out_dir, K, dev, "GauS_%04d.png", save=save, tables=(lut_depth, lut_diff))
+    ws, lpips_ws = workspace(W, H, dev), None
+    with torch.no_grad():
+        means2D = torch.zeros_like(p["means3D"])
+        for k, (color_u8, depth, _) in enumerate(sequence):
+            if depth.dtype == torch.uint16:
+                depth = depth.view(torch.int16)
+            if extended:
+                gt_color, gt_depth = _ops.ingest_ex(color_u8.to(dev), depth.to(dev), sequence.png_depth_scale, (W, H), distortion=distortion,
+                                                    intrinsics=sequence.intrinsics)
+            else:
+                gt_color, gt_depth = _ops.ingest(color_u8.to(dev), depth.to(dev), sequence.png_depth_scale, (W, H))
+            pkg = _render.render(settings[k], p["means3D"], means2D, p["opacities"], shs=p.get("shs"), colors_precomp=p.get("colors_precomp"),
+                                 scales=p["scales"], rotations=p["rotations"])
+            frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, use_weight_norm=use_weight_norm, eps=eps,
+                          depth_near=depth_near, depth_far=depth_far, clamp_color=True, out=rows[k], ws=ws)
+            if lpips is not None:
+                if lpips_ws is None:
+                    lpips_ws = lpips.workspace(W, H)
+                lpips.frame(pkg["render_color"], gt_color, gt_depth, out=lpips_rows[k], ws=lpips_ws)
+            dump.frame(k, pkg, gt_depth, "nvs", use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
+    host, view = rows.cpu().numpy(), dump.rows.cpu().numpy()
+    res = dict(per_frame=host, view_per_frame=view, psnr=host[:, EVAL_PSNR].copy(), ms_ssim=host[:, EVAL_MS_SSIM].copy(),
+               depth_rmse=view[:, view_dump.RMSE].copy(), depth_l1=view[:, view_dump.L1].copy())
+    if lpips is not None:
+        res["lpips_per_frame"] = lpips_rows.cpu().numpy()
+        res["lpips"] = res["lpips_per_frame"][:, LPIPS_VALUE].copy()
+    for name in ("psnr", "ms_ssim", "depth_rmse", "depth_l1") + (("lpips",) if lpips is not None else ()):
+        res["mean_" + name] = float(res[name].mean())
+    stamps = dict(rasterizer=_lib.build_info(), map=_map_lib.build_info(), front=_front_lib.build_info(), view=_view_lib.build_info())
+    if extended:
+        stamps["ingest"] = _ingest_lib.build_info()
+    if lpips is not None:
+        stamps["lpips"] = _lpips_lib.build_info()
+    res["result"] = {NVS_KEYS[0]: res["mean_psnr"], NVS_KEYS[1]: res["mean_ms_ssim"], NVS_KEYS[2]: res.get("mean_lpips"),
+                     NVS_KEYS[3]: res["mean_depth_rmse"], NVS_KEYS[4]: res["mean_depth_l1"], "build": stamps}
+    if out_dir is not None:
+        for name, key in (("psnr.txt", "psnr"), ("rmse.txt", "depth_rmse"), ("l1.txt", "depth_l1"), ("ssim.txt", "ms_ssim"), ("lpips.txt", "lpips")):
+            if key in res:
+                np.savetxt(os.path.join(out_dir, name), res[key])
+        with open(os.path.join(out_dir, "nvs_result.json"), "w") as fh:
+            json.dump(res["result"], fh, indent=2)
     return res

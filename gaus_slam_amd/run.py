@@ -1,6 +1,6 @@
 """The runner: a reference-format configuration file in, the results of one SLAM run out.
 
-    python -m gaus_slam_amd.run CONFIG.py [--frames N] [--out DIR] [--seed S]
+    python -m gaus_slam_amd.run CONFIG.py [--frames N] [--out DIR] [--seed S] [--save-scene]
 
 CONFIG.py is a Python file that defines `config` (configs/*/config*.py of the reference), loaded with runpy.  Its `data` section
 names the recorded sequence (datasets.open_sequence: gradslam_data_cfg, basedir, sequence, start, end, stride, ignore_bad;
@@ -9,7 +9,9 @@ desired_image_height / desired_image_width become config['cameras']['height'] / 
 2).  --frames N keeps the first N frames of the selection.  The run is slam.run_slam, then SlamResult.evaluate() and
 SlamResult.save(DIR): results.json, traj_est.txt, traj_gt.txt and map.ply -- the loop and the tail of the reference's
 scripts/gaus.py without wandb and without the Open3D windows.  DIR defaults to config['workdir'] / config['run_name'] where the
-file names both, else to ./output."""
+file names both, else to ./output.  --save-scene also writes DIR/save, the reference's saved scene (scene_io.save_scene: the
+configuration as run, the raw map and both trajectories), which python -m gaus_slam_amd.nvs evaluates later; without the flag
+the four files above are all that is written."""
 import argparse
 import copy
 import os
@@ -54,6 +56,7 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--save-scene", action="store_true")
     a = ap.parse_args(argv)
     config = load_config(a.config)
     seed = a.seed if a.seed is not None else int(config.get("seed", 0))
@@ -70,6 +73,8 @@ def main(argv=None):
         return 2
     result = slam.run_slam(seq, config, seed=seed)
     m = result.save(out, data=config["data"], seed=seed)
+    if a.save_scene:
+        result.save_scene(os.path.join(out, "save"), config)
     print(f"{len(seq)} frames, {len(result.records)} local maps, {result.backend.map.soa.P} Gaussians: mean PSNR {m['mean_psnr']:.2f} dB, "
           f"mean depth L1 {m['mean_depth_l1']:.5f} m, ATE RMSE {m['ate_rmse']:.5f} m -> {out}")
     return 0

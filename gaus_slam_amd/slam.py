@@ -491,6 +491,14 @@ class SlamResult:
         write_map(os.path.join(directory, "map.ply"), self.backend.map.soa.views)
         return evaluation
 
+    def save_scene(self, directory, config=None):
+        """scene_io.save_scene of the run into `directory`: config.json (`config`, or the driver's own configuration when None),
+        gaussians.ply (the global map's raw parameters), w2cs.npz.npy and gt_w2cs.npz.npy -- what the reference's save_scence
+        leaves under <run>/save for a later evaluation (python -m gaus_slam_amd.nvs)."""
+        from . import scene_io
+        scene_io.save_scene(directory, self.backend.config if config is None else config, self.backend.map.soa.views, self.trajectory(),
+                            self.gt_trajectory())
+
     def trajectory(self):
         return self.backend.trajectory()
 
