@@ -285,6 +285,64 @@ class ScanNetPPSequence(RecordedSequence):
         self.image_names = [names[k] for k in self.retained]
 
 
+PREFETCH_THREAD = "gaus_slam_amd.datasets.prefetch"  # the name of every reader thread prefetch() starts
+
+
+def prefetch(sequence, depth=2):
+    """A generator over the frames of `sequence`, in order -- sequence.frame(k) for k < len(sequence) where the reader has that
+    method, else its items as iteration gives them -- read ahead by ONE daemon thread through a queue of `depth` entries, so
+    that decoding frame k + 1 (Pillow releases the interpreter lock inside its decoders) overlaps what the consumer does with
+    frame k.  The thread only reads: it touches no GPU and calls nothing of torch's device API.  An exception in the reader
+    travels through the queue and is raised in the consumer at the position of the frame that caused it, after every frame
+    before it.  Closing the generator, or dropping it, tells the thread to stop and empties the queue, so a reader blocked on a
+    full queue wakes, sees the flag and ends after at most the frame it is decoding; the generator waits for that.  depth=0 is
+    plain iteration, without a thread."""
+    import queue
+    import threading
+    depth = int(depth)
+    if depth < 0:
+        raise ValueError(f"depth must be >= 0, got {depth}")
+
+    def items():
+        if hasattr(sequence, "frame") and hasattr(sequence, "__len__"):
+            return (sequence.frame(k) for k in range(len(sequence)))
+        return iter(sequence)
+
+    if depth == 0:
+        yield from items()
+        return
+    q, stop = queue.Queue(maxsize=depth), threading.Event()
+    ITEM, END, ERROR = 0, 1, 2
+
+    def reader():
+        try:
+            for item in items():
+                q.put((ITEM, item))
+                if stop.is_set():
+                    return
+            q.put((END, None))
+        except BaseException as e:  # handed to the consumer, whatever it is
+            q.put((ERROR, e))
+
+    thread = threading.Thread(target=reader, name=PREFETCH_THREAD, daemon=True)
+    thread.start()
+    try:
+        while True:
+            kind, value = q.get()
+            if kind == END:
+                return
+            if kind == ERROR:
+                raise value
+            yield value
+    finally:
+        stop.set()
+        while thread.is_alive():  # every put that was waiting for room gets it; the reader then sees the flag
+            try:
+                q.get_nowait()
+            except queue.Empty:
+                thread.join(0.001)
+
+
 READERS = {"replica": ReplicaSequence, "tum": TUMSequence, "scannet": ScanNetSequence, "scannetpp": ScanNetPPSequence}
 
 

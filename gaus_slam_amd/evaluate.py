@@ -14,13 +14,16 @@ row per frame in a device tensor and reads the host once at the end.
     res = evaluate_map(params, frames, lpips=lpips.LPIPS.from_files(alex, lin))    # also lpips, mean_lpips (eval.py:409-410)
     res = evaluate_map(params, frames, dump_dir="eval")                            # also eval_final's saved images
     res = evaluate_nvs(params, seq, (876, 584), out_dir="run/nvs_result")          # eval_nvs (eval.py:120-251) on held-out views
+    res = evaluate_final(params, seq, (W, H), est, gt, out_dir="run/eval_result", mesh=True)   # eval_final itself: EVERY frame of
+                                                                                   # the sequence re-read, its mesh and the mesh's score
 
 LPIPS is gaus_slam_amd/lpips.py (include/gs2d_lpips.h): a model built from the two weight files a user of the reference has on
 disk; no weights ship here and none are fetched.  The published network's weights were never available to this project, so the
 agreement with torchmetrics on them is unverified: what is verified is the arithmetic on random weights and the loader's key
 mapping.  The saved images (the render, the colour-mapped depth and depth difference) are gaus_slam_amd/view_dump.py
-(include/gs2d_view.h): bytes made on the device, one copy per frame, PNGs written with Pillow.  Not covered: the mesh metrics
-of utils/eval_mesh.py.  The TSDF mesh itself is gaus_slam_amd/tsdf.py.
+(include/gs2d_view.h): bytes made on the device, one copy per frame, PNGs written with Pillow.  The TSDF mesh is gaus_slam_amd/tsdf.py
+and tsdf_blocks.py, the mesh metrics of utils/eval_mesh.py are meshrender.py and recon.py; evaluate_final strings them together
+as eval_final does.  The three loops (evaluate_map, evaluate_nvs, evaluate_final) share one frame body, _Loop.
 
 No CPU fallback: CPU tensors, wrong shapes, dtypes or strides raise RuntimeError."""
 import json
@@ -142,58 +145,77 @@ def evaluate_map(params, frames, *, est_w2cs=None, gt_w2cs=None, use_weight_norm
     launches and one copy of 9 H W bytes per frame) and is written as eval_final writes it (eval.py:357-376):
     rendering/rgb/GauS_%04d.png, rendering/depth/GauS_%04d.png and rendering/diff/differ_%04d.png.  The result gains `view_per_frame`,
     the [K, view_dump.OUT_DOUBLES] array.  With dump_dir=None nothing changes: the same launches and the same bits."""
-    from . import render as _render
     require(len(frames) >= 1, "frames is empty")
     if tsdf is not None:
         require(mesh_intrinsics is not None, "tsdf needs mesh_intrinsics: (fx, fy, cx, cy) or a 3x3 matrix")
         require(int(mesh_interval) >= 1, "mesh_interval must be >= 1")
         require(mesh_extrinsics is None or len(mesh_extrinsics) == len(frames), "mesh_extrinsics must have one matrix per frame")
     require((est_w2cs is None) == (gt_w2cs is None), "est_w2cs and gt_w2cs go together")
-    p = dict(params)
-    colors = p.pop("colors", None)
-    if colors is not None:
-        p["colors_precomp"] = colors
-    dev = p["means3D"].device
-    require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
-    rows = torch.empty((len(frames), EVAL_OUT_DOUBLES), dtype=torch.float64, device=dev)
-    ws = None
-    lpips_rows = None if lpips is None else torch.empty((len(frames), LPIPS_OUT_DOUBLES), dtype=torch.float64, device=dev)
-    lpips_ws = None
-    dump = None if dump_dir is None else _Dump(dump_dir, len(frames), dev, "differ_%04d.png")
+    kw = dict(use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
+    loop = _Loop(params, len(frames), lpips, clamp_color, kw)
+    dump = None if dump_dir is None else _Dump(dump_dir, len(frames), loop.dev, "differ_%04d.png")
     with torch.no_grad():
-        means2D = torch.zeros_like(p["means3D"])
         for k, (settings, gt_color, gt_depth) in enumerate(frames):
-            pkg = _render.render(settings, p["means3D"], means2D, p["opacities"], shs=p.get("shs"), colors_precomp=p.get("colors_precomp"),
-                                 scales=p["scales"], rotations=p["rotations"])
-            W, H = int(pkg["allmap"].shape[2]), int(pkg["allmap"].shape[1])
-            if ws is None or ws.numel() < _map_lib.lib().gs2d_eval_ws_bytes(W, H):
-                ws = workspace(W, H, dev)
-            frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, use_weight_norm=use_weight_norm, eps=eps,
-                          depth_near=depth_near, depth_far=depth_far, clamp_color=clamp_color, out=rows[k], ws=ws)
-            if lpips is not None:
-                if lpips_ws is None or lpips_ws.numel() < lpips.ws_bytes(W, H):
-                    lpips_ws = lpips.workspace(W, H)
-                lpips.frame(pkg["render_color"], gt_color, gt_depth, out=lpips_rows[k], ws=lpips_ws)
+            pkg = loop.frame(k, settings, gt_color, gt_depth)
             if dump is not None:
-                dump.frame(k, pkg, gt_depth, "final", use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
+                dump.frame(k, pkg, gt_depth, "final", **kw)
             if tsdf is not None and k % int(mesh_interval) == 0:
                 w2c = mesh_extrinsics[k] if mesh_extrinsics is not None else settings.viewmatrix.reshape(4, 4).t().contiguous()
-                tsdf.integrate_render(pkg["render_color"], pkg["allmap"], mesh_intrinsics, w2c, use_weight_norm=use_weight_norm,
-                                      eps=eps, depth_near=depth_near, depth_far=depth_far)
-    host = rows.cpu().numpy()
-    res = dict(per_frame=host)
-    for name, col in (("psnr", EVAL_PSNR), ("ms_ssim", EVAL_MS_SSIM), ("depth_rmse", EVAL_DEPTH_RMSE), ("depth_l1", EVAL_DEPTH_L1)):
-        res[name] = host[:, col].copy()
-        res["mean_" + name] = float(host[:, col].mean())
-    if lpips is not None:
-        res["lpips_per_frame"] = lpips_rows.cpu().numpy()
-        res["lpips"] = res["lpips_per_frame"][:, LPIPS_VALUE].copy()
-        res["mean_lpips"] = float(res["lpips"].mean())
+                tsdf.integrate_render(pkg["render_color"], pkg["allmap"], mesh_intrinsics, w2c, **kw)
+    res = loop.result()
     if dump is not None:
         res["view_per_frame"] = dump.rows.cpu().numpy()
     if est_w2cs is not None:
         res["ate_rmse"] = ate_rmse(est_w2cs, gt_w2cs)
     return res
+
+
+class _Loop:
+    """The frame body the three loops share (evaluate_map, evaluate_nvs, evaluate_final): the view rendered with the existing
+    operator, frame_metrics into row k of one [K, EVAL_OUT_DOUBLES] device tensor and, with a model, lpips.frame into row k of a
+    second; the workspaces are made for the first frame and kept.  The caller holds torch.no_grad()."""
+
+    def __init__(self, params, n_frames, lpips, clamp_color, kw):
+        p = dict(params)
+        colors = p.pop("colors", None)
+        if colors is not None:
+            p["colors_precomp"] = colors
+        require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
+        self.p, self.dev, self.lpips, self.clamp_color, self.kw = p, p["means3D"].device, lpips, clamp_color, kw
+        self.rows = torch.empty((n_frames, EVAL_OUT_DOUBLES), dtype=torch.float64, device=self.dev)
+        self.lpips_rows = None if lpips is None else torch.empty((n_frames, LPIPS_OUT_DOUBLES), dtype=torch.float64, device=self.dev)
+        self.means2D = torch.zeros_like(p["means3D"])
+        self.ws = self.lpips_ws = None
+
+    def frame(self, k, settings, gt_color, gt_depth):
+        """Renders view k and scores it; returns the operator's package."""
+        from . import render as _render
+        p, lpips = self.p, self.lpips
+        pkg = _render.render(settings, p["means3D"], self.means2D, p["opacities"], shs=p.get("shs"), colors_precomp=p.get("colors_precomp"),
+                             scales=p["scales"], rotations=p["rotations"])
+        W, H = int(pkg["allmap"].shape[2]), int(pkg["allmap"].shape[1])
+        if self.ws is None or self.ws.numel() < _map_lib.lib().gs2d_eval_ws_bytes(W, H):
+            self.ws = workspace(W, H, self.dev)
+        frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, clamp_color=self.clamp_color, out=self.rows[k], ws=self.ws,
+                      **self.kw)
+        if lpips is not None:
+            if self.lpips_ws is None or self.lpips_ws.numel() < lpips.ws_bytes(W, H):
+                self.lpips_ws = lpips.workspace(W, H)
+            lpips.frame(pkg["render_color"], gt_color, gt_depth, out=self.lpips_rows[k], ws=self.lpips_ws)
+        return pkg
+
+    def result(self):
+        """The host read: per_frame, psnr, ms_ssim, depth_rmse, depth_l1 (lpips_per_frame, lpips) and their means."""
+        host = self.rows.cpu().numpy()
+        res = dict(per_frame=host)
+        for name, col in (("psnr", EVAL_PSNR), ("ms_ssim", EVAL_MS_SSIM), ("depth_rmse", EVAL_DEPTH_RMSE), ("depth_l1", EVAL_DEPTH_L1)):
+            res[name] = host[:, col].copy()
+            res["mean_" + name] = float(host[:, col].mean())
+        if self.lpips is not None:
+            res["lpips_per_frame"] = self.lpips_rows.cpu().numpy()
+            res["lpips"] = res["lpips_per_frame"][:, LPIPS_VALUE].copy()
+            res["mean_lpips"] = float(res["lpips"].mean())
+        return res
 
 
 class _Dump:
@@ -249,72 +271,215 @@ def evaluate_nvs(params, sequence, size, *, intrinsics=None, use_sa=True, use_we
     view_dump.frame_images, None for colormaps.JET / PLASMA.
     Returns a dict: per-frame float64 arrays psnr, ms_ssim, depth_rmse, depth_l1 (lpips), their means mean_*, per_frame and
     view_per_frame (the whole row arrays), and result (what nvs_result.json holds)."""
-    from . import _front_lib, _ingest_lib, _lib, _lpips_lib, _view_lib, frontend_ops as _ops, render as _render, view_dump
+    from . import frontend_ops as _ops, view_dump
     W, H = int(size[0]), int(size[1])
     K = len(sequence)
     require(K >= 1, "sequence is empty")
-    p = dict(params)
-    colors = p.pop("colors", None)
-    if colors is not None:
-        p["colors_precomp"] = colors
-    require(p["means3D"].is_cuda, "params must be CUDA tensors (no CPU fallback)")
-    dev = p["means3D"].device
-    W0, H0 = sequence.size
+    kw = dict(use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
+    loop = _Loop(params, K, lpips, True, kw)
+    dev = loop.dev
+    ingest = _Ingest(sequence, (W, H), dev)
     if intrinsics is None:
-        intrinsics = _ops.scaled_intrinsics(sequence.intrinsics, (W0, H0), (W, H))
-    distortion = getattr(sequence, "distortion", None)
-    extended = distortion is not None or tuple(getattr(sequence, "depth_size", None) or (W0, H0)) != (W0, H0)
+        intrinsics = ingest.scaled_intrinsics
     poses = getattr(sequence, "poses", None)
     if poses is None:
         poses = [c2w for _, _, c2w in sequence]
     c2ws = torch.stack([torch.as_tensor(np.asarray(m)).to(torch.float32) for m in poses]).to(dev).contiguous()
     rel = _ops.compose(_ops.compose(c2ws[0].contiguous(), inv_a=True), c2ws, ia=[0] * K)  # relative_pose=True of the reference's datasets
     settings = _ops.cameras(W, H, intrinsics, rel, inv_a=True, use_sa=use_sa)
-    rows = torch.empty((K, EVAL_OUT_DOUBLES), dtype=torch.float64, device=dev)
-    lpips_rows = None if lpips is None else torch.empty((K, LPIPS_OUT_DOUBLES), dtype=torch.float64, device=dev)
     save = bool(save_renders) and out_dir is not None
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
     dump = _Dump(out_dir, K, dev, "GauS_%04d.png", save=save, tables=(lut_depth, lut_diff))
-    ws, lpips_ws = workspace(W, H, dev), None
     with torch.no_grad():
-        means2D = torch.zeros_like(p["means3D"])
         for k, (color_u8, depth, _) in enumerate(sequence):
-            if depth.dtype == torch.uint16:
-                depth = depth.view(torch.int16)
-            if extended:
-                gt_color, gt_depth = _ops.ingest_ex(color_u8.to(dev), depth.to(dev), sequence.png_depth_scale, (W, H), distortion=distortion,
-                                                    intrinsics=sequence.intrinsics)
-            else:
-                gt_color, gt_depth = _ops.ingest(color_u8.to(dev), depth.to(dev), sequence.png_depth_scale, (W, H))
-            pkg = _render.render(settings[k], p["means3D"], means2D, p["opacities"], shs=p.get("shs"), colors_precomp=p.get("colors_precomp"),
-                                 scales=p["scales"], rotations=p["rotations"])
-            frame_metrics(pkg["render_color"], pkg["allmap"], gt_color, gt_depth, use_weight_norm=use_weight_norm, eps=eps,
-                          depth_near=depth_near, depth_far=depth_far, clamp_color=True, out=rows[k], ws=ws)
-            if lpips is not None:
-                if lpips_ws is None:
-                    lpips_ws = lpips.workspace(W, H)
-                lpips.frame(pkg["render_color"], gt_color, gt_depth, out=lpips_rows[k], ws=lpips_ws)
-            dump.frame(k, pkg, gt_depth, "nvs", use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
-    host, view = rows.cpu().numpy(), dump.rows.cpu().numpy()
-    res = dict(per_frame=host, view_per_frame=view, psnr=host[:, EVAL_PSNR].copy(), ms_ssim=host[:, EVAL_MS_SSIM].copy(),
-               depth_rmse=view[:, view_dump.RMSE].copy(), depth_l1=view[:, view_dump.L1].copy())
-    if lpips is not None:
-        res["lpips_per_frame"] = lpips_rows.cpu().numpy()
-        res["lpips"] = res["lpips_per_frame"][:, LPIPS_VALUE].copy()
+            gt_color, gt_depth = ingest(color_u8, depth)
+            pkg = loop.frame(k, settings[k], gt_color, gt_depth)
+            dump.frame(k, pkg, gt_depth, "nvs", **kw)
+    res, view = loop.result(), dump.rows.cpu().numpy()
+    res.update(view_per_frame=view, depth_rmse=view[:, view_dump.RMSE].copy(), depth_l1=view[:, view_dump.L1].copy())
     for name in ("psnr", "ms_ssim", "depth_rmse", "depth_l1") + (("lpips",) if lpips is not None else ()):
         res["mean_" + name] = float(res[name].mean())
-    stamps = dict(rasterizer=_lib.build_info(), map=_map_lib.build_info(), front=_front_lib.build_info(), view=_view_lib.build_info())
-    if extended:
-        stamps["ingest"] = _ingest_lib.build_info()
-    if lpips is not None:
-        stamps["lpips"] = _lpips_lib.build_info()
     res["result"] = {NVS_KEYS[0]: res["mean_psnr"], NVS_KEYS[1]: res["mean_ms_ssim"], NVS_KEYS[2]: res.get("mean_lpips"),
-                     NVS_KEYS[3]: res["mean_depth_rmse"], NVS_KEYS[4]: res["mean_depth_l1"], "build": stamps}
+                     NVS_KEYS[3]: res["mean_depth_rmse"], NVS_KEYS[4]: res["mean_depth_l1"],
+                     "build": _stamps(ingest.extended, lpips is not None, view=True)}
     if out_dir is not None:
-        for name, key in (("psnr.txt", "psnr"), ("rmse.txt", "depth_rmse"), ("l1.txt", "depth_l1"), ("ssim.txt", "ms_ssim"), ("lpips.txt", "lpips")):
-            if key in res:
-                np.savetxt(os.path.join(out_dir, name), res[key])
-        with open(os.path.join(out_dir, "nvs_result.json"), "w") as fh:
-            json.dump(res["result"], fh, indent=2)
+        _write_tables(out_dir, res, "nvs_result.json")
     return res
+
+
+class _Ingest:
+    """One sensor frame of `sequence` into the working tensors at size = (W, H) on `device`, through the launch run_slam
+    chooses: ingest_ex for a sequence with a distortion or a depth size of its own, ingest for every other."""
+
+    def __init__(self, sequence, size, device):
+        from . import frontend_ops as _ops
+        self._ops, self.seq, self.size, self.dev = _ops, sequence, size, device
+        W0, H0 = sequence.size
+        self.distortion = getattr(sequence, "distortion", None)
+        self.extended = self.distortion is not None or tuple(getattr(sequence, "depth_size", None) or (W0, H0)) != (W0, H0)
+
+    @property
+    def scaled_intrinsics(self):
+        return self._ops.scaled_intrinsics(self.seq.intrinsics, self.seq.size, self.size)
+
+    def __call__(self, color_u8, depth):
+        seq, dev = self.seq, self.dev
+        if depth.dtype == torch.uint16:  # the same bits under a dtype every copy supports
+            depth = depth.view(torch.int16)
+        if self.extended:
+            return self._ops.ingest_ex(color_u8.to(dev), depth.to(dev), seq.png_depth_scale, self.size, distortion=self.distortion,
+                                       intrinsics=seq.intrinsics)
+        return self._ops.ingest(color_u8.to(dev), depth.to(dev), seq.png_depth_scale, self.size)
+
+
+def _stamps(extended, with_lpips, view=False, vol=False, mesh=False):
+    """build_info() of the libraries an evaluation loop used, as nvs_result.json and result.json carry them under `build`."""
+    from . import _front_lib, _ingest_lib, _lib, _lpips_lib, _mesh_lib, _view_lib, _vol_lib
+    stamps = dict(rasterizer=_lib.build_info(), map=_map_lib.build_info(), front=_front_lib.build_info())
+    for name, used, mod in (("view", view, _view_lib), ("ingest", extended, _ingest_lib), ("lpips", with_lpips, _lpips_lib),
+                            ("vol", vol, _vol_lib), ("mesh", mesh, _mesh_lib)):
+        if used:
+            stamps[name] = mod.build_info()
+    return stamps
+
+
+def _write_tables(out_dir, res, json_name):
+    """psnr.txt, rmse.txt, l1.txt, ssim.txt, (lpips.txt) and res['result'] as `json_name`: the files of eval.py:452-456 / :482."""
+    for name, key in (("psnr.txt", "psnr"), ("rmse.txt", "depth_rmse"), ("l1.txt", "depth_l1"), ("ssim.txt", "ms_ssim"), ("lpips.txt", "lpips")):
+        if key in res:
+            np.savetxt(os.path.join(out_dir, name), res[key])
+    with open(os.path.join(out_dir, json_name), "w") as fh:
+        json.dump(res["result"], fh, indent=2)
+
+
+FINAL_KEYS = ("PSNR: ", "SSIM: ", "LPIPS: ", "Depth RMSE: ", "Depth L1: ", "ATE RMSE: ")  # eval.py:437-444, verbatim
+SCANNETPP_SWAP = ((0.0, 1.0, 0.0, 0.0), (-1.0, 0.0, 0.0, 0.0), (0.0, 0.0, 1.0, 0.0), (0.0, 0.0, 0.0, 1.0))  # P of eval.py:389-396
+COMPENSATE_VECTOR = (-0.0, 2.5 / 512.0, -2.5 / 512.0)  # eval.py:461-462 at scale 1; every entry is a float32
+
+
+def _plain(v):
+    """Tensors and arrays as lists, for json."""
+    if isinstance(v, torch.Tensor):
+        return v.detach().cpu().tolist()
+    if hasattr(v, "tolist"):
+        return v.tolist()
+    if isinstance(v, dict):
+        return {str(k): _plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    return v
+
+
+def evaluate_final(params, sequence, size, est_w2cs, gt_w2cs, *, intrinsics=None, use_sa=True, use_weight_norm=True, eps=1e-6,
+                   depth_near=1e-2, depth_far=1e2, lpips=None, out_dir=None, save_renders=False, mesh=False, mesh_interval=5,
+                   dataset_name=None, gt_mesh=None, unseen=None, prefetch=2, seed=0, n_views=1000):
+    """eval_final (eval.py:254-485) over EVERY frame of a sequence: the streaming twin of evaluate_nvs for the training views, and
+    the protocol behind the numbers the reference reports for a run.  params: the activated leaves, as for evaluate_map.
+    sequence: any reader run_slam accepts.  size: the working (W, H); intrinsics: (fx, fy, cx, cy) or a 3x3 at that size, None
+    for the sequence's own, scaled.  est_w2cs, gt_w2cs: [K,4,4], the run's trajectories relative to the first frame, as
+    SlamResult.trajectory() and scene_io.load_scene give them; a sequence of another length raises before anything is rendered.
+    Per frame k: ingest / ingest_ex (chosen as run_slam does) of the frame datasets.prefetch hands over -- `prefetch` frames are
+    decoded ahead by one host thread, 0 for plain iteration --, the render at est_w2cs[k] under torch.no_grad(), with the raster
+    settings of all K views from one frontend_ops.cameras launch, frame_metrics(clamp_color=False) into row k of one device
+    tensor, lpips.frame with a model into row k of a second, and with save_renders (which needs out_dir) view_dump.frame_images
+    in "final" mode and the three PNGs under the names evaluate_map(dump_dir=...) writes.  The rows are read once at the end.
+    The ATE is ate_rmse(est_w2cs, gt_w2cs), which drops the frames whose ground-truth pose is not finite.
+    mesh: every mesh_interval-th render is fused (integrate_render, uint8 colour) into a tsdf_blocks.BlockTSDFVolume at its
+    defaults, the reference's, in the dataset's world frame: E[k] = est_w2cs[k] @ inv(c2w_0) @ P, with c2w_0 the sequence's first
+    absolute pose (non-finite: RuntimeError) and P = SCANNETPP_SWAP when dataset_name.lower() == "scannetpp", else the identity
+    (eval.py:389-399); F = inv(c2w_0) @ P is one frontend_ops.compose launch and all E one more.  The extracted mesh, its
+    vertices moved by COMPENSATE_VECTOR in float32, goes to out_dir/mesh/final_mesh.ply.  gt_mesh: (vertices [V,3], triangles
+    [T,3]) of the ground truth, arrays or tensors.  The mesh is then cleaned (meshrender.clean_mesh; mesh/cleaned_mesh.ply) and
+    scored: meshrender.evaluate_mesh(clean=False, seed=seed, n_views=n_views; 1000 views are the reference's) when `unseen`
+    ([N,3] points no view may see) is given or the dataset is not ScanNet++; for ScanNet++ recon.evaluate_reconstruction alone with "depth_l1": None, the reference's 2-D metric being
+    unsupported there (eval.py:479).  The dict goes to out_dir/reconstruction_metrics.json.
+    With out_dir: psnr.txt, rmse.txt, l1.txt, ssim.txt, (lpips.txt) and result.json -- FINAL_KEYS with the means and the ATE,
+    "LPIPS: " null without a model, plus `build`, the stamps of the libraries used.
+    Returns a dict: per-frame float64 arrays psnr, ms_ssim, depth_rmse, depth_l1 (lpips), their means mean_*, per_frame,
+    ate_rmse, result and, with mesh, mesh_extrinsics ([K,4,4] on the device) and mesh (vertices, colors, triangles on the
+    device), and with gt_mesh, reconstruction."""
+    from . import datasets, frontend_ops as _ops
+    W, H = int(size[0]), int(size[1])
+    est = est_w2cs if isinstance(est_w2cs, torch.Tensor) else torch.stack([torch.as_tensor(m) for m in est_w2cs])
+    require(est.dim() == 3 and tuple(est.shape[1:]) == (4, 4), f"est_w2cs must be [K,4,4], got {tuple(est.shape)}")
+    K = int(est.shape[0])
+    require(len(sequence) == K, f"the sequence holds {len(sequence)} frames, the trajectory {K} poses")
+    require(K >= 1, "sequence is empty")
+    require(int(mesh_interval) >= 1, "mesh_interval must be >= 1")
+    require(not save_renders or out_dir is not None, "save_renders needs out_dir")
+    require(gt_mesh is None or mesh, "gt_mesh needs mesh=True")
+    kw = dict(use_weight_norm=use_weight_norm, eps=eps, depth_near=depth_near, depth_far=depth_far)
+    loop = _Loop(params, K, lpips, False, kw)
+    dev = loop.dev
+    ingest = _Ingest(sequence, (W, H), dev)
+    if intrinsics is None:
+        intrinsics = ingest.scaled_intrinsics
+    est = est.detach().to(dev, torch.float32).contiguous()
+    settings = _ops.cameras(W, H, intrinsics, est, use_sa=use_sa)
+    scannetpp = str(dataset_name).lower() == "scannetpp"
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    dump = _Dump(out_dir, K, dev, "differ_%04d.png") if save_renders else None
+    volume = extrinsics = None
+    if mesh:
+        from . import tsdf_blocks
+        volume = tsdf_blocks.BlockTSDFVolume(device=dev)
+    with torch.no_grad():
+        for k, (color_u8, depth, gt_c2w) in enumerate(datasets.prefetch(sequence, prefetch)):
+            if mesh and k == 0:
+                c2w_0 = torch.as_tensor(np.asarray(gt_c2w)).to(torch.float32)  # relative_pose=False: the absolute first pose
+                require(tuple(c2w_0.shape) == (4, 4) and bool(torch.isfinite(c2w_0).all()),
+                        "the sequence's first pose is not finite: the mesh cannot be placed in the dataset's world")
+                swap = torch.tensor(SCANNETPP_SWAP) if scannetpp else torch.eye(4)
+                F = _ops.compose(c2w_0.to(dev).contiguous(), swap.to(dev), inv_a=True)
+                extrinsics = _ops.compose(est, F)
+            gt_color, gt_depth = ingest(color_u8, depth)
+            pkg = loop.frame(k, settings[k], gt_color, gt_depth)
+            if dump is not None:
+                dump.frame(k, pkg, gt_depth, "final", **kw)
+            if mesh and k % int(mesh_interval) == 0:
+                volume.integrate_render(pkg["render_color"], pkg["allmap"], intrinsics, extrinsics[k], rgb8=True, **kw)
+    res = loop.result()
+    res["ate_rmse"] = ate_rmse(est, gt_w2cs)
+    cleaned = False
+    if mesh:
+        vertices, colors, triangles = volume.extract_mesh()
+        vertices = vertices + torch.tensor(COMPENSATE_VECTOR, dtype=torch.float32, device=dev)
+        res["mesh_extrinsics"], res["mesh"] = extrinsics, (vertices, colors, triangles)
+        if out_dir is not None:
+            from . import ply
+            ply.save_mesh(os.path.join(out_dir, "mesh", "final_mesh.ply"), vertices, colors, triangles)
+        if gt_mesh is not None:
+            res["reconstruction"] = _score_mesh(res["mesh"], gt_mesh, unseen, scannetpp, seed, n_views, out_dir)
+            cleaned = True
+    res["result"] = {FINAL_KEYS[0]: res["mean_psnr"], FINAL_KEYS[1]: res["mean_ms_ssim"], FINAL_KEYS[2]: res.get("mean_lpips"),
+                     FINAL_KEYS[3]: res["mean_depth_rmse"], FINAL_KEYS[4]: res["mean_depth_l1"], FINAL_KEYS[5]: res["ate_rmse"],
+                     "build": _stamps(ingest.extended, lpips is not None, view=dump is not None, vol=mesh, mesh=cleaned)}
+    if out_dir is not None:
+        _write_tables(out_dir, res, "result.json")
+    return res
+
+
+def _score_mesh(mesh, gt_mesh, unseen, scannetpp, seed, n_views, out_dir):
+    """clean_mesh of the fused mesh (written as mesh/cleaned_mesh.ply), then its score against the ground truth as
+    utils/eval_mesh.py:259-291 composes it; the dict also goes to reconstruction_metrics.json."""
+    from . import meshrender, ply, recon
+    dev = mesh[0].device
+    gt_v = torch.as_tensor(np.asarray(gt_mesh[0].cpu() if isinstance(gt_mesh[0], torch.Tensor) else gt_mesh[0], dtype=np.float32)).to(dev).contiguous()
+    gt_t = torch.as_tensor(np.asarray(gt_mesh[1].cpu() if isinstance(gt_mesh[1], torch.Tensor) else gt_mesh[1], dtype=np.int32)).to(dev).contiguous()
+    if unseen is not None:
+        unseen = torch.as_tensor(np.asarray(unseen.cpu() if isinstance(unseen, torch.Tensor) else unseen, dtype=np.float32)).to(dev).contiguous()
+    vertices, colors, triangles = meshrender.clean_mesh(*mesh)
+    require(vertices.shape[0] >= 1 and triangles.shape[0] >= 1, "nothing is left of the fused mesh after clean_mesh")
+    if out_dir is not None:
+        ply.save_mesh(os.path.join(out_dir, "mesh", "cleaned_mesh.ply"), vertices, colors, triangles)
+    if unseen is not None or not scannetpp:
+        out = meshrender.evaluate_mesh(vertices, colors, triangles, gt_v, gt_t, unseen=unseen, clean=False, seed=seed, n_views=n_views)
+    else:
+        out = recon.evaluate_reconstruction(vertices, triangles, gt_v, gt_t, seed=seed)
+        out["depth_l1"] = None
+    if out_dir is not None:
+        with open(os.path.join(out_dir, "reconstruction_metrics.json"), "w") as fh:
+            json.dump(_plain(out), fh, indent=2)
+    return out

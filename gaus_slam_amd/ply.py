@@ -157,6 +157,144 @@ def save_mesh(path, vertices, colors, triangles):
         fh.write(face.tobytes())
 
 
+_COUNT_TYPES = ("uchar", "uint8", "int", "int32")
+_INDEX_TYPES = ("int", "int32", "uint", "uint32")
+_INDEX_NAMES = ("vertex_indices", "vertex_index")
+
+
+def _mesh_header(fh, path):
+    """-> (format, [(element name, count, [(property name, type) or (property name, count type, index type)])])."""
+    if fh.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = fh.readline()
+        if not line:
+            raise ValueError(f"{path}: the PLY header is not terminated")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format" and len(tok) >= 2:
+            fmt = tok[1]
+        elif tok[0] == "element" and len(tok) == 3 and tok[2].isdigit():
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property" and elements and len(tok) == 5 and tok[1] == "list":
+            elements[-1][2].append((tok[4], tok[2], tok[3]))
+        elif tok[0] == "property" and elements and len(tok) == 3 and tok[1] in _PLY_TYPES:
+            elements[-1][2].append((tok[2], tok[1]))
+        elif tok[0] == "end_header":
+            return fmt, elements
+        else:
+            raise ValueError(f"{path}: the header line {line.decode('ascii', 'replace').strip()!r} is not understood")
+
+
+def read_triangle_mesh(path):
+    """-> (vertices float32 [V,3], triangles int32 [T,3]) on the host, of a triangle mesh other tools wrote (a ground-truth mesh
+    of Replica or ScanNet++; MeshLab, Open3D, trimesh): `ascii` or `binary_little_endian`; a `vertex` element whose x, y, z are
+    float or double, every further scalar property (normals, colours, quality) skipped by its declared size; then a `face`
+    element with ONE list property, vertex_indices or vertex_index, counted in uchar / uint8 / int and indexed in int / int32 /
+    uint / uint32, further scalar properties skipped; elements after `face` are ignored.  Binary faces are one structured numpy
+    read when every count is 3.  ValueError, naming the file and the cause, for faces that are not triangles (with their
+    number), a missing x, y or z, a list property in `vertex`, a big-endian file, a truncated body and an index >= V."""
+    with open(path, "rb") as fh:
+        fmt, elements = _mesh_header(fh, path)
+        if fmt == "binary_big_endian":
+            raise ValueError(f"{path}: big-endian PLY files are not supported")
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError(f"{path}: unsupported PLY format {fmt!r}")
+        if len(elements) < 2 or elements[0][0] != "vertex" or elements[1][0] != "face":
+            raise ValueError(f"{path}: a `vertex` and then a `face` element are expected, got {[e[0] for e in elements]}")
+        (_, nv, vprops), (_, nf, fprops) = elements[0], elements[1]
+        if any(len(p) == 3 for p in vprops):
+            raise ValueError(f"{path}: a list property in the `vertex` element is not supported")
+        for axis in "xyz":
+            kinds = [t for n, t in vprops if n == axis]
+            if not kinds:
+                raise ValueError(f"{path}: the `vertex` element lacks the property {axis!r}")
+            if _PLY_TYPES[kinds[0]] not in ("<f4", "<f8"):
+                raise ValueError(f"{path}: the vertex property {axis!r} must be float or double, got {kinds[0]}")
+        lists = [p for p in fprops if len(p) == 3]
+        if len(lists) != 1 or lists[0][0] not in _INDEX_NAMES:
+            raise ValueError(f"{path}: the `face` element must hold one list property named vertex_indices or vertex_index")
+        _, count_type, index_type = lists[0]
+        if count_type not in _COUNT_TYPES or index_type not in _INDEX_TYPES:
+            raise ValueError(f"{path}: the face list is `{count_type} {index_type}`; the count must be one of {_COUNT_TYPES}, the index one "
+                             f"of {_INDEX_TYPES}")
+        at = fprops.index(lists[0])
+        if fmt == "ascii":
+            tokens = fh.read().split()
+            n = nv * len(vprops)
+            if len(tokens) < n:
+                raise ValueError(f"{path}: the body is truncated: {len(tokens)} numbers for {nv} vertices of {len(vprops)} properties")
+            table = np.array(tokens[:n], dtype=np.float64).reshape(nv, len(vprops))
+            xyz = np.stack([table[:, [p[0] for p in vprops].index(a)] for a in "xyz"], 1)
+            tri = _ascii_faces(tokens[n:], nf, at, len(fprops) - at - 1, path)
+        else:
+            vert = np.fromfile(fh, np.dtype([(f"{j}_{p[0]}", _PLY_TYPES[p[1]]) for j, p in enumerate(vprops)]), nv)
+            if len(vert) != nv:
+                raise ValueError(f"{path}: the body is truncated: {len(vert)} of {nv} vertices")
+            xyz = np.stack([vert[f"{[p[0] for p in vprops].index(a)}_{a}"] for a in "xyz"], 1)
+            pre = [(f"{j}_{p[0]}", _PLY_TYPES[p[1]]) for j, p in enumerate(fprops[:at])]
+            post = [(f"{at + 1 + j}_{p[0]}", _PLY_TYPES[p[1]]) for j, p in enumerate(fprops[at + 1:])]
+            tri = _binary_faces(fh.read(), nf, pre, _PLY_TYPES[count_type], _PLY_TYPES[index_type], post, path)
+    tri = tri.astype(np.int64).reshape(-1, 3)
+    if len(tri) and (int(tri.min()) < 0 or int(tri.max()) >= nv):
+        raise ValueError(f"{path}: a face refers to the vertex {int(tri.max()) if int(tri.max()) >= nv else int(tri.min())}, the file holds {nv} vertices")
+    return np.ascontiguousarray(xyz, dtype=np.float32), np.ascontiguousarray(tri, dtype=np.int32)
+
+
+def _not_triangles(path, bad, nf):
+    return ValueError(f"{path}: {bad} of {nf} faces are not triangles")
+
+
+def _binary_faces(buf, nf, pre, count_t, index_t, post, path):
+    """[nf,3] indices from the bytes after the vertex table.  One structured view when every count is 3; otherwise the faces are
+    walked once, only to say how many are not triangles or that the body ends early."""
+    face = np.dtype(pre + [("n", count_t), ("v", index_t, (3,))] + post)
+    if len(buf) >= nf * face.itemsize:
+        rows = np.frombuffer(buf, face, nf)
+        if (rows["n"] == 3).all():
+            return rows["v"]
+    n_pre, n_post = np.dtype(pre).itemsize if pre else 0, np.dtype(post).itemsize if post else 0
+    count, index = np.dtype(count_t), np.dtype(index_t)
+    o = bad = 0
+    for _ in range(nf):
+        o += n_pre
+        if o + count.itemsize > len(buf):
+            raise ValueError(f"{path}: the body is truncated inside the `face` element")
+        n = int(np.frombuffer(buf, count, 1, o)[0])
+        if n < 0:
+            raise ValueError(f"{path}: a face has the vertex count {n}")
+        o += count.itemsize + n * index.itemsize + n_post
+        bad += n != 3
+    if o > len(buf):
+        raise ValueError(f"{path}: the body is truncated inside the `face` element")
+    raise _not_triangles(path, bad, nf)
+
+
+def _ascii_faces(tokens, nf, n_pre, n_post, path):
+    """[nf,3] indices from the numbers after the vertex table; a face is n_pre scalars, the count, that many indices, n_post
+    scalars.  One array when every count is 3; otherwise a walk, as for binary files."""
+    row = n_pre + 4 + n_post
+    if len(tokens) >= nf * row:
+        rows = np.array(tokens[:nf * row], dtype=np.float64).reshape(nf, row)
+        if (rows[:, n_pre] == 3).all():
+            return rows[:, n_pre + 1:n_pre + 4]
+    o = bad = 0
+    for _ in range(nf):
+        o += n_pre
+        if o >= len(tokens):
+            raise ValueError(f"{path}: the body is truncated inside the `face` element")
+        n = int(float(tokens[o]))
+        if n < 0:
+            raise ValueError(f"{path}: a face has the vertex count {n}")
+        o += 1 + n + n_post
+        bad += n != 3
+    if o > len(tokens):
+        raise ValueError(f"{path}: the body is truncated inside the `face` element")
+    raise _not_triangles(path, bad, nf)
+
+
 def read_mesh(path):
     """-> (vertices [V,3] float32, colors [V,3] uint8, triangles [T,3] int32) of a file save_mesh wrote (that header exactly)."""
     with open(path, "rb") as fh:

@@ -1,6 +1,6 @@
 """The runner: a reference-format configuration file in, the results of one SLAM run out.
 
-    python -m gaus_slam_amd.run CONFIG.py [--frames N] [--out DIR] [--seed S] [--save-scene]
+    python -m gaus_slam_amd.run CONFIG.py [--frames N] [--out DIR] [--seed S] [--save-scene] [--eval-final]
 
 CONFIG.py is a Python file that defines `config` (configs/*/config*.py of the reference), loaded with runpy.  Its `data` section
 names the recorded sequence (datasets.open_sequence: gradslam_data_cfg, basedir, sequence, start, end, stride, ignore_bad;
@@ -11,7 +11,12 @@ SlamResult.save(DIR): results.json, traj_est.txt, traj_gt.txt and map.ply -- the
 scripts/gaus.py without wandb and without the Open3D windows.  DIR defaults to config['workdir'] / config['run_name'] where the
 file names both, else to ./output.  --save-scene also writes DIR/save, the reference's saved scene (scene_io.save_scene: the
 configuration as run, the raw map and both trajectories), which python -m gaus_slam_amd.nvs evaluates later; without the flag
-the four files above are all that is written."""
+the four files above are all that is written.  --eval-final then re-reads the sequence and scores EVERY frame at its estimated
+pose (SlamResult.evaluate_final, the reference's eval_final) into DIR/final_refine_result, the directory scripts/gaus.py uses:
+result.json is the reference's protocol, results.json the score of the frames the maps were optimised on.  The configuration's
+`eval` section (eval_mesh, save_renders, mesh_interval) says whether a mesh is fused and the renders are saved; without one there
+is no mesh, there are no renders and the interval is 5.  The ground-truth mesh is looked for as python -m gaus_slam_amd.eval_final
+does."""
 import argparse
 import copy
 import os
@@ -57,6 +62,7 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--save-scene", action="store_true")
+    ap.add_argument("--eval-final", action="store_true")
     a = ap.parse_args(argv)
     config = load_config(a.config)
     seed = a.seed if a.seed is not None else int(config.get("seed", 0))
@@ -77,6 +83,16 @@ def main(argv=None):
         result.save_scene(os.path.join(out, "save"), config)
     print(f"{len(seq)} frames, {len(result.records)} local maps, {result.backend.map.soa.P} Gaussians: mean PSNR {m['mean_psnr']:.2f} dB, "
           f"mean depth L1 {m['mean_depth_l1']:.5f} m, ATE RMSE {m['ate_rmse']:.5f} m -> {out}")
+    if a.eval_final:
+        from . import eval_final
+        ev, data = config.get("eval") or {}, config["data"]
+        mesh = bool(ev.get("eval_mesh", False))
+        gt_mesh, unseen = eval_final.ground_truth(data, prog="gaus_slam_amd.run") if mesh else (None, None)
+        final = os.path.join(out, "final_refine_result")
+        res = result.evaluate_final(seq, out_dir=final, mesh=mesh, save_renders=bool(ev.get("save_renders", False)),
+                                    mesh_interval=int(ev.get("mesh_interval", 5)), dataset_name=eval_final.dataset_name(data),
+                                    gt_mesh=gt_mesh, unseen=unseen)
+        print(eval_final.summary(len(seq), res, final))
     return 0
 
 

@@ -521,6 +521,16 @@ class SlamResult:
         return evaluate.evaluate_map(b.activated_params(), frames, est_w2cs=self.trajectory(), gt_w2cs=self.gt_trajectory(),
                                      **{**_render_kw(b.config), **kw})
 
+    def evaluate_final(self, sequence, **kw):
+        """evaluate.evaluate_final on the global map over EVERY frame of `sequence`, the one the run was made from, re-read and
+        rendered at its estimated pose: the reference's eval_final, whose numbers are the ones it reports.  The working size,
+        the intrinsics, use_sa and the depth normalisation are the run's own; kw: what evaluate_final takes besides (out_dir,
+        mesh, mesh_interval, save_renders, lpips, dataset_name, gt_mesh, unseen, prefetch, seed)."""
+        from . import evaluate
+        b = self.backend
+        return evaluate.evaluate_final(b.activated_params(), sequence, (b.W, b.H), self.trajectory(), self.gt_trajectory(),
+                                       **{"intrinsics": b.intr, "use_sa": b.use_sa, **_render_kw(b.config), **kw})
+
 
 def run_slam(sequence, config, seed=0, device="cuda"):
     """The loop of scripts/gaus.py:84-104 over `sequence`: any iterable of (color_u8 [H0,W0,3] uint8, depth [H0,W0] uint16 or
