@@ -10,7 +10,8 @@ tail (C ABI in include/gs2d_lpips.h, sources in csrc_lpips/), and the frontend l
 decision and batched camera set-up (C ABI in include/gs2d_front.h, sources in csrc_front/), and the ingest library: the sensor-frame
 ingest with separate colour and depth sizes and colour undistortion (C ABI in include/gs2d_ingest.h, sources in csrc_ingest/),
 and the view library: the saved images of a rendered view and its depth errors (C ABI in include/gs2d_view.h, sources in
-csrc_view/).
+csrc_view/), and the viz library: the observer renderer of a replayed run -- a coloured mesh, lines over it, the frame as bytes
+(C ABI in include/gs2d_viz.h, sources in csrc_viz/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -92,6 +93,13 @@ CSRC_VIEW = os.path.join(_HERE, "csrc_view")
 VIEW_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_view_hip.so")
 VIEW_SOURCES = ["gs2d_view.hip"]
 VIEW_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_view.h")]
+
+# The observer renderer of a replay is an eleventh library, for the same reason.  It includes nothing of csrc/ or csrc_mesh/ and
+# restates the triangle setup, cull and walk of csrc_mesh/gs2d_mesh.hip.
+CSRC_VIZ = os.path.join(_HERE, "csrc_viz")
+VIZ_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_viz_hip.so")
+VIZ_SOURCES = ["gs2d_viz.hip"]
+VIZ_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_viz.h")]
 
 
 def _hash(directory, headers):
@@ -295,8 +303,24 @@ def build_view(force=False, verbose=False):
     return _compile(VIEW_LIB_PATH, [os.path.join(CSRC_VIEW, f) for f in VIEW_SOURCES], "GS2D_VIEW_SOURCE_HASH", view_source_hash(), verbose)
 
 
+def viz_source_hash():
+    """source_hash() of the viz library: every file under csrc_viz/ plus VIZ_HEADERS (gs2d_viz_build_info reports it)."""
+    return _hash(CSRC_VIZ, VIZ_HEADERS)
+
+
+def _viz_stale():
+    deps = [os.path.join(CSRC_VIZ, f) for f in os.listdir(CSRC_VIZ)] + VIZ_HEADERS
+    return _is_stale(VIZ_LIB_PATH, viz_source_hash(), deps)
+
+
+def build_viz(force=False, verbose=False):
+    if not force and not _viz_stale():
+        return VIZ_LIB_PATH
+    return _compile(VIZ_LIB_PATH, [os.path.join(CSRC_VIZ, f) for f in VIZ_SOURCES], "GS2D_VIZ_SOURCE_HASH", viz_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the ten libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the eleven libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
@@ -306,6 +330,7 @@ def build(force=False, verbose=False):
     build_front(force, verbose)
     build_ingest(force, verbose)
     build_view(force, verbose)
+    build_viz(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -324,3 +349,4 @@ if __name__ == "__main__":
     print(FRONT_LIB_PATH)
     print(INGEST_LIB_PATH)
     print(VIEW_LIB_PATH)
+    print(VIZ_LIB_PATH)
