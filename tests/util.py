@@ -240,10 +240,17 @@ def _hip_forward(sc, use_sa, bg, shs, sh_degree, transMat_precomp, scale_modifie
     args = (t(np.asarray(bg, np.float32)), means3D, colors, opac, scales, rots, scale_modifier, tm,
             t(cam.viewmatrix), t(cam.projmatrix), cam.tanfovx, cam.tanfovy, cam.H, cam.W, sh, sh_degree,
             t(cam.campos), use_sa, False, debug)
-    R, color, allmap, radii, geom, binning, img = rasterizer.rasterize_gaussians(*args)
+    res = rasterizer.rasterize_gaussians(*args)
     torch.cuda.synchronize()
+    return unpack_forward(res, args, means3D.shape[0], cam.W, cam.H, debug)
+
+
+def unpack_forward(res, args, P, W, H, debug=False):
+    """hip_forward's dict from what rasterize_gaussians returned (or one frame of rasterize_gaussians_batch) for `args`, its
+    argument tuple.  args None (a batch frame: no single call could be repeated in debug mode): no "keys"."""
+    from gaus_slam_amd import _lib, rasterizer
+    R, color, allmap, radii, geom, binning, img = res
     L = _lib.lib()
-    P, W, H = means3D.shape[0], cam.W, cam.H
     gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
     go = (C.c_size_t * 5)(); bo = (C.c_size_t * 2)(); io = (C.c_size_t * 2)()
     L.gs2d_geometry_layout(P, go); L.gs2d_binning_layout(R, bo); L.gs2d_image_layout(W, H, io)
@@ -260,13 +267,13 @@ def _hip_forward(sc, use_sa, bg, shs, sh_degree, transMat_precomp, scale_modifie
         out["point_list"] = view(b, bo[0], np.uint32, R) if R > 0 else np.zeros(0, np.uint32)
         # the full 64-bit sorted keys are materialised only in debug mode (the product path keeps packed (depth, id)
         # pairs and writes just the point list): fetch them from a second, debug-mode forward of the same inputs
-        if R > 0 and not debug:
+        if args is not None and R > 0 and not debug:
             dbg_args = args[:-1] + (True,)
             R2, _, _, _, _, binning2, _ = rasterizer.rasterize_gaussians(*dbg_args)
             torch.cuda.synchronize()
             assert R2 == R
             out["keys"] = view(binning2.cpu().numpy(), bo[1], np.uint64, R)
-        else:
+        elif args is not None:
             out["keys"] = view(b, bo[1], np.uint64, R) if R > 0 else np.zeros(0, np.uint64)
         out["ranges"] = view(im, io[0], np.uint32, gx * gy * 2).reshape(gx * gy, 2)
         plane = gx * gy * 256
