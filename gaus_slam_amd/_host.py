@@ -1,7 +1,7 @@
 """Host helpers shared by everything above the C ABIs (the headers under include/): the ONE way a binding loads its library and
 applies its table of prototypes (`load`), the source hash inside a build info (`source_hash_of`), device pointers, torch's
 current stream, the allocator callback the libraries ask for scratch memory through, and the ONE sequence every library call
-runs (`call`).  Imports torch and ctypes only, nothing from this package: the eleven bindings (_lib.py, _map_lib.py, ...) hold a
+runs (`call`).  Imports torch and ctypes only, nothing from this package: the twelve bindings (_lib.py, _map_lib.py, ...) hold a
 table each and sit on top of this module, the operator modules on top of those."""
 import ctypes as C
 import itertools

@@ -11,7 +11,8 @@ decision and batched camera set-up (C ABI in include/gs2d_front.h, sources in cs
 ingest with separate colour and depth sizes and colour undistortion (C ABI in include/gs2d_ingest.h, sources in csrc_ingest/),
 and the view library: the saved images of a rendered view and its depth errors (C ABI in include/gs2d_view.h, sources in
 csrc_view/), and the viz library: the observer renderer of a replayed run -- a coloured mesh, lines over it, the frame as bytes
-(C ABI in include/gs2d_viz.h, sources in csrc_viz/).
+(C ABI in include/gs2d_viz.h, sources in csrc_viz/), and the gs3d library: the 3D-Gaussian ablation rasterizer, a second differentiable
+rasterizer with its own preprocess, binning and blend kernels (C ABI in include/gs3d_rasterizer.h, sources in csrc_gs3d/).
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only container as well as on the GPU box.
 The .so files are written in-tree (gaus_slam_amd/lib/) so they travel with the source snapshot.
@@ -100,6 +101,14 @@ CSRC_VIZ = os.path.join(_HERE, "csrc_viz")
 VIZ_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_viz_hip.so")
 VIZ_SOURCES = ["gs2d_viz.hip"]
 VIZ_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_viz.h")]
+
+# The 3D-Gaussian ablation rasterizer is a twelfth library, for the same reason.  It includes ../csrc/gs2d_tile_sort.h (and with
+# it gs2d_scan.h and gs2d_common.h) unchanged for the scan and the per-tile depth sort, so its hash covers those three as well.
+CSRC_GS3D = os.path.join(_HERE, "csrc_gs3d")
+GS3D_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_gs3d_hip.so")
+GS3D_SOURCES = ["gs3d_geom.hip", "gs3d_blend.hip", "gs3d_api.hip"]
+GS3D_HEADERS = [os.path.join(_HERE, "..", "include", "gs3d_rasterizer.h")] + [os.path.join(CSRC, f) for f in
+                                                                               ("gs2d_tile_sort.h", "gs2d_scan.h", "gs2d_common.h")]
 
 
 def _hash(directory, headers):
@@ -319,8 +328,25 @@ def build_viz(force=False, verbose=False):
     return _compile(VIZ_LIB_PATH, [os.path.join(CSRC_VIZ, f) for f in VIZ_SOURCES], "GS2D_VIZ_SOURCE_HASH", viz_source_hash(), verbose)
 
 
+def gs3d_source_hash():
+    """source_hash() of the gs3d library: every file under csrc_gs3d/ plus GS3D_HEADERS, the C-ABI header and the three headers
+    of csrc/ it is compiled with (gs3d_build_info reports it)."""
+    return _hash(CSRC_GS3D, GS3D_HEADERS)
+
+
+def _gs3d_stale():
+    deps = [os.path.join(CSRC_GS3D, f) for f in os.listdir(CSRC_GS3D)] + GS3D_HEADERS
+    return _is_stale(GS3D_LIB_PATH, gs3d_source_hash(), deps)
+
+
+def build_gs3d(force=False, verbose=False):
+    if not force and not _gs3d_stale():
+        return GS3D_LIB_PATH
+    return _compile(GS3D_LIB_PATH, [os.path.join(CSRC_GS3D, f) for f in GS3D_SOURCES], "GS3D_SOURCE_HASH", gs3d_source_hash(), verbose)
+
+
 def build(force=False, verbose=False):
-    """Builds the eleven libraries (each only when stale); returns the path of the rasterizer library."""
+    """Builds the twelve libraries (each only when stale); returns the path of the rasterizer library."""
     build_map(force, verbose)
     build_mesh(force, verbose)
     build_loss(force, verbose)
@@ -331,6 +357,7 @@ def build(force=False, verbose=False):
     build_ingest(force, verbose)
     build_view(force, verbose)
     build_viz(force, verbose)
+    build_gs3d(force, verbose)
     if not force and not _stale():
         return LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
@@ -350,3 +377,4 @@ if __name__ == "__main__":
     print(INGEST_LIB_PATH)
     print(VIEW_LIB_PATH)
     print(VIZ_LIB_PATH)
+    print(GS3D_LIB_PATH)

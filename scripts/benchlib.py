@@ -1,4 +1,4 @@
-"""The one measurement protocol of the map-side benches (covis_bench, densify_bench, densify_grad_bench, eval_bench, eval_final_bench, ingest_bench, localmap_merge_bench, loss_bench, lpips_bench,
+"""The one measurement protocol of the map-side benches (covis_bench, densify_bench, densify_grad_bench, eval_bench, eval_final_bench, gs3d_bench, ingest_bench, localmap_merge_bench, loss_bench, lpips_bench,
 mapping_raw_bench, mesh_depth_bench, nvs_bench, recon_bench, replay_bench, slam_bench, tracking_loop_bench, tsdf_bench, tsdf_blocks_bench) and the few lines the two parity dumps share.  torch and the standard library
 only; gaus_slam_amd is imported where it is first needed, so that a dump can choose its tree before that.
 
