@@ -94,65 +94,105 @@ def preprocess(means3D, scales, rotations, scale_modifier, viewmatrix, projmatri
                 num_rendered=int(((x1 - x0) * (y1 - y0))[visible].sum()))
 
 
+def _depth_key(z):
+    """The sort key of the operator: the float32 depth's bits (depths of visible Gaussians are positive, so the bits order as
+    the values do)."""
+    return z.detach().to(torch.float32).view(torch.int32)
+
+
 def render(means3D, colors, opacities, scales, rotations, scale_modifier, viewmatrix, projmatrix, tanfovx, tanfovy, W, H, background,
-           means2D=None):
+           means2D=None, window=False):
     """Returns a dict: color [NC,H,W] (differentiable), depth [H,W], radii [P], num_rendered, mask [H,W] (knife-edge pixels),
-    flagged [P], n_contrib [H,W] (splats composited)."""
+    flagged [P], n_contrib [H,W] (splats composited), last_pos [H,W] (the 1-based position, within the pixel's tile list, of the
+    last splat the pixel composited, 0 if none: what the operator stores as n_contrib), final_T, visible.
+    The order is a stable sort by the float32 depth, ties by index: the operator's contract.  window=True evaluates each Gaussian
+    on the pixels of its tile rectangle only (it is exactly zero elsewhere): the same forward bits, for frames of many tiles."""
     dt = means3D.dtype
     g = preprocess(means3D, scales, rotations, scale_modifier, viewmatrix, projmatrix, tanfovx, tanfovy, W, H, means2D)
     vis = torch.nonzero(g["visible"]).reshape(-1)
-    zs = g["z"].detach()[vis]
-    order = vis[torch.sort(zs, stable=True)[1]]  # stable: equal depths keep the Gaussians' order
+    order = vis[torch.sort(_depth_key(g["z"][vis]), stable=True)[1]]  # stable: equal depths keep the Gaussians' order
     NC = colors.shape[1]
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
-    tile_x, tile_y = (xs / TILE).to(torch.int64), (ys / TILE).to(torch.int64)
+    ys_f, xs_f = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
+    tile_x_f, tile_y_f = (xs_f / TILE).to(torch.int64), (ys_f / TILE).to(torch.int64)
     T = torch.ones((H, W), dtype=dt)
     done = torch.zeros((H, W), dtype=torch.bool)
     out = [torch.zeros((H, W), dtype=dt) for _ in range(NC)]
     depth = torch.zeros((H, W), dtype=dt)
     mask = torch.zeros((H, W), dtype=torch.bool)
     n_contrib = torch.zeros((H, W), dtype=torch.int64)
+    position = torch.zeros((H, W), dtype=torch.int64)  # of the current splat in the pixel's tile list, 1-based
+    last_pos = torch.zeros((H, W), dtype=torch.int64)
     opac = opacities.reshape(-1)
     recent = []  # (z, rectangle) of the splats before this one whose depth is within REL of its own
     for i in order.tolist():
         x0, x1, y0, y1 = g["rect"][i].tolist()
+        if window:
+            r0, r1, c0, c1 = y0 * TILE, min(y1 * TILE, H), x0 * TILE, min(x1 * TILE, W)
+            sl = (slice(r0, r1), slice(c0, c1))
+            cut = lambda t: t[sl]
+            spread = lambda t: torch.nn.functional.pad(t, (c0, W - c1, r0, H - r1))
+        else:
+            sl = (slice(None), slice(None))
+            cut = spread = lambda t: t
+        xs, ys, tile_x, tile_y = cut(xs_f), cut(ys_f), cut(tile_x_f), cut(tile_y_f)
+        Tw, done_w = cut(T), cut(done)
         in_rect = (tile_x >= x0) & (tile_x < x1) & (tile_y >= y0) & (tile_y < y1)
         z = g["z"][i]
         zf = float(z.detach())
-        recent = [(pz, pr) for pz, pr in recent if zf - pz <= REL * abs(zf)]
-        for _, (px0, px1, py0, py1) in recent:  # two depths (nearly) equal: float32 may order them the other way
-            mask |= in_rect & ~done & (tile_x >= px0) & (tile_x < px1) & (tile_y >= py0) & (tile_y < py1)
-        recent.append((zf, (x0, x1, y0, y1)))
+        zbits = int(_depth_key(z))
+        recent = [(pz, pb, pr) for pz, pb, pr in recent if zf - pz <= REL * abs(zf)]
+        for _, pb, (px0, px1, py0, py1) in recent:  # two depths nearly equal: float32 may order them the other way
+            if pb != zbits:  # (the same float32 depth: both sides order the pair by index)
+                mask[sl] |= in_rect & ~done_w & (tile_x >= px0) & (tile_x < px1) & (tile_y >= py0) & (tile_y < py1)
+        recent.append((zf, zbits, (x0, x1, y0, y1)))
         A, B, Cc = g["conic"][i]
         dx, dy = g["centre"][i, 0] - xs, g["centre"][i, 1] - ys
         power = -0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy
         raw = opac[i] * torch.exp(torch.clamp(power, max=0.0))
         alpha = torch.clamp(raw, max=0.99)
-        live = in_rect & ~done
+        live = in_rect & ~done_w
         pw, rw, aw = power.detach(), raw.detach(), alpha.detach()
         contributes = live & (pw <= 0) & (aw >= 1.0 / 255.0)
-        test_T = T * (1 - alpha)
+        test_T = Tw * (1 - alpha)
         stops = contributes & (test_T.detach() < 1e-4)
         composite = contributes & ~stops
         # knife edges, where they can change the outcome
         Ad, Bd, Cd = g["conic"][i].detach().abs().tolist()
         terms = (0.5 * (Ad * dx * dx + Cd * dy * dy) + Bd * (dx * dy).abs()).detach()  # what the sum that is power is made of
-        mask |= live & (pw.abs() <= REL * terms) & (terms > 0)
-        mask |= live & (pw <= 0) & (_near(rw, 1.0 / 255.0) | _near(rw, 0.99))
-        mask |= contributes & _near(test_T.detach(), 1e-4)
-        w = torch.where(composite, alpha * T, torch.zeros_like(T))
+        mask[sl] |= live & (pw.abs() <= REL * terms) & (terms > 0)
+        mask[sl] |= live & (pw <= 0) & (_near(rw, 1.0 / 255.0) | _near(rw, 0.99))
+        mask[sl] |= contributes & _near(test_T.detach(), 1e-4)
+        w = spread(torch.where(composite, alpha * Tw, torch.zeros_like(Tw)))
         for k in range(NC):
             out[k] = out[k] + colors[i, k] * w
         depth = depth + z.detach() * w.detach()
-        T = torch.where(composite, test_T, T)
-        done = done | stops
-        n_contrib += composite
+        T = torch.where(spread(composite), spread(test_T), T)
+        done[sl] |= stops
+        n_contrib[sl] += composite
+        position[sl] += in_rect
+        last_pos[sl] = torch.where(composite, cut(position), cut(last_pos))
     color = torch.stack([out[k] + T * background[k] for k in range(NC)])
     return dict(color=color, depth=depth, radii=g["radius"], num_rendered=g["num_rendered"], mask=mask, flagged=g["flagged"],
-                n_contrib=n_contrib, final_T=T.detach(), visible=g["visible"])
+                n_contrib=n_contrib, last_pos=last_pos, final_T=T.detach(), visible=g["visible"])
 
 
-def forward_backward(inputs, cam, W, H, background, dL_dout, dtype):
+def tile_lists(g, W, H):
+    """The binning of a preprocess() result: (lists, ranges).  lists[tile] holds the ids of the visible Gaussians whose rectangle
+    contains the tile (tile = y * gx + x), in list order: a stable sort by the float32 depth's bits, ties by index.  ranges
+    [tiles,2] int64 is the exclusive scan of the lists' lengths: (begin, end) into the concatenated point list."""
+    gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
+    vis = torch.nonzero(g["visible"]).reshape(-1)
+    order = vis[torch.sort(_depth_key(g["z"][vis]), stable=True)[1]]
+    rect = g["rect"][order]
+    tile = torch.arange(gx * gy)
+    tx, ty = (tile % gx)[:, None], (tile // gx)[:, None]
+    member = (rect[None, :, 0] <= tx) & (tx < rect[None, :, 1]) & (rect[None, :, 2] <= ty) & (ty < rect[None, :, 3])
+    lists = [order[row] for row in member]
+    ends = torch.cumsum(member.sum(1), 0)
+    return lists, torch.stack([ends - member.sum(1), ends], 1)
+
+
+def forward_backward(inputs, cam, W, H, background, dL_dout, dtype, scale_modifier=1.0, window=False):
     """inputs: dict of means3D, colors, opacities, scales, rotations (any float dtype); cam: (viewmatrix, projmatrix, tanfovx,
     tanfovy).  Returns (render dict, grads dict) computed in `dtype`.  grads: means2D (with respect to the NDC centre, [P,3]
     with z = 0), colors, opacities, means3D, scales, rotations."""
@@ -160,8 +200,8 @@ def forward_backward(inputs, cam, W, H, background, dL_dout, dtype):
     vm, pm, tfx, tfy = cam
     P = leaves["means3D"].shape[0]
     means2D = torch.zeros((P, 3), dtype=dtype, requires_grad=True)  # the NDC centre's offset, a leaf of its own
-    r = render(leaves["means3D"], leaves["colors"], leaves["opacities"], leaves["scales"], leaves["rotations"], 1.0, vm.to(dtype),
-               pm.to(dtype), tfx, tfy, W, H, background.to(dtype), means2D)
+    r = render(leaves["means3D"], leaves["colors"], leaves["opacities"], leaves["scales"], leaves["rotations"], scale_modifier,
+               vm.to(dtype), pm.to(dtype), tfx, tfy, W, H, background.to(dtype), means2D, window=window)
     loss = (r["color"] * dL_dout.to(dtype)).sum()
     names = ["means3D", "colors", "opacities", "scales", "rotations"]
     if P == 0 or not loss.requires_grad:

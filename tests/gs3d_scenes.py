@@ -97,13 +97,12 @@ def scene_B(P, seed=0):
                  rng.uniform(0, 1, (P, 6)))
 
 
-def scene_C(seed=SEEDS["C"]):
+def scene_C(seed=SEEDS["C"], P=60):
     """33 x 17 under a strongly rotated camera, anisotropic scales spanning 100 : 1."""
     rng = np.random.default_rng(seed)
     W, H, intr = 33, 17, (25.0, 21.0, 15.1, 9.3)
     w2c = _w2c(rng, 2.1, [0.4, -0.3, 0.5])
-    P = 60
-    z = rng.uniform(0.5, 3.0, P)
+    z =rng.uniform(0.5, 3.0, P)
     pts = np.stack([rng.uniform(-0.7, 0.7, P) * z, rng.uniform(-0.45, 0.45, P) * z, z], 1)
     base = rng.uniform(0.003, 0.006, (P, 1)) * z[:, None]
     ratio = np.stack([np.ones(P), 10.0 ** rng.uniform(0, 2, P), np.full(P, 100.0)], 1)
@@ -111,12 +110,11 @@ def scene_C(seed=SEEDS["C"]):
     return _pack(W, H, intr, w2c, pts, sc, _quats(rng, P), rng.uniform(0.2, 0.95, P), rng.uniform(0, 1, (P, 6)))
 
 
-def scene_D(seed=SEEDS["D"]):
+def scene_D(seed=SEEDS["D"], P=2100):
     """16 x 16 with one tile list longer than the depth sort's LDS capacity (2048), forward only: every splat is faint."""
     rng = np.random.default_rng(seed)
     W, H, intr = 16, 16, (14.0, 15.0, 8.2, 7.6)
     w2c = _w2c(rng, 0.2, [0.0, 0.1, 0.0])
-    P = 2100
     z = 1.0 + 0.001 * rng.permutation(P)
     pts = [_at_pixel(rng.uniform(1, 15), rng.uniform(1, 15), zk, *intr) for zk in z]
     sc = rng.uniform(1.0, 3.0, (P, 3)) * z[:, None] / 14.0
