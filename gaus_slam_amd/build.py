@@ -55,12 +55,15 @@ LOSS_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_loss_hip.so")
 LOSS_SOURCES = ["gs2d_loss_ex.hip"]
 LOSS_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_loss.h")]
 
-# The block-hashed TSDF volume is a fifth library: tests pin the map library's symbols, headers and hash, so it restates the
-# integration rule and the tetrahedron table of csrc_map/gs2d_tsdf.hip.  It includes ../csrc/gs2d_scan.h and gs2d_common.h only.
+# The block-hashed TSDF volume is a fifth library: tests pin the map library's symbols and C-ABI headers.  The integration rule and
+# the tetrahedron table are the dense volume's: it includes csrc_map/gs2d_tsdf_rule.h (and with it gs2d_depth_rule.h), so its
+# hash covers those two as well and a change to the rule rebuilds both libraries.  Of csrc/ it includes gs2d_scan.h and
+# gs2d_common.h.
 CSRC_VOL = os.path.join(_HERE, "csrc_vol")
 VOL_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_vol_hip.so")
 VOL_SOURCES = ["gs2d_vol.hip"]
-VOL_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_vol.h")]
+VOL_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_vol.h")] + [os.path.join(CSRC_MAP, f) for f in
+                                                                        ("gs2d_tsdf_rule.h", "gs2d_depth_rule.h")]
 
 # The keyframe bank is a sixth library: every older library's exported symbols are pinned by its host test.  It includes nothing
 # of csrc/.
@@ -95,12 +98,13 @@ VIEW_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_view_hip.so")
 VIEW_SOURCES = ["gs2d_view.hip"]
 VIEW_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_view.h")]
 
-# The observer renderer of a replay is an eleventh library, for the same reason.  It includes nothing of csrc/ or csrc_mesh/ and
-# restates the triangle setup, cull and walk of csrc_mesh/gs2d_mesh.hip.
+# The observer renderer of a replay is an eleventh library, for the same reason.  It includes nothing of csrc/.  The triangle
+# setup, cull, pixel test and walk are the mesh library's: it includes csrc_mesh/gs2d_tri_raster.h, so its hash covers that
+# header as well and a change to the rasterizer rebuilds both libraries.
 CSRC_VIZ = os.path.join(_HERE, "csrc_viz")
 VIZ_LIB_PATH = os.path.join(LIB_DIR, "libgs2d_viz_hip.so")
 VIZ_SOURCES = ["gs2d_viz.hip"]
-VIZ_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_viz.h")]
+VIZ_HEADERS = [os.path.join(_HERE, "..", "include", "gs2d_viz.h"), os.path.join(CSRC_MESH, "gs2d_tri_raster.h")]
 
 # The 3D-Gaussian ablation rasterizer is a twelfth library, for the same reason.  It includes ../csrc/gs2d_tile_sort.h (and with
 # it gs2d_scan.h and gs2d_common.h) unchanged for the scan and the per-tile depth sort, so its hash covers those three as well.
@@ -215,7 +219,8 @@ def build_loss(force=False, verbose=False):
 
 
 def vol_source_hash():
-    """source_hash() of the volume library: every file under csrc_vol/ plus VOL_HEADERS (gs2d_vol_build_info reports it)."""
+    """source_hash() of the volume library: every file under csrc_vol/ plus VOL_HEADERS, the C-ABI header and the two rule headers
+    of csrc_map/ it is compiled with (gs2d_vol_build_info reports it)."""
     return _hash(CSRC_VOL, VOL_HEADERS)
 
 
@@ -313,7 +318,8 @@ def build_view(force=False, verbose=False):
 
 
 def viz_source_hash():
-    """source_hash() of the viz library: every file under csrc_viz/ plus VIZ_HEADERS (gs2d_viz_build_info reports it)."""
+    """source_hash() of the viz library: every file under csrc_viz/ plus VIZ_HEADERS, the C-ABI header and the rasterizer header
+    of csrc_mesh/ it is compiled with (gs2d_viz_build_info reports it)."""
     return _hash(CSRC_VIZ, VIZ_HEADERS)
 
 

@@ -1,12 +1,14 @@
 // What the sources of libgs2d_map_hip.so share; not part of the C ABI (that is include/gs2d_map.h, include/gs2d_pose.h and include/gs2d_eval.h).
 //   host:   the thread's error text, pointer and launch checks, the workspace layout of the select / write pairs, the table
 //           of arrays a topology change moves
-//   device: pytorch3d's two quaternion conversions, the normalised depth of a rendered view, the row copy of the write kernels,
+//   device: pytorch3d's two quaternion conversions, the normalised depth of a rendered view (gs2d_depth_rule.h, which the volume
+//           library shares), the row copy of the write kernels,
 //           the fixed-order double sums of a wave and of a workgroup
 // Everything but the two error functions has internal linkage, so every source compiles its own copy.
 #pragma once
 #include "../csrc/gs2d_common.h"
 #include "../../include/gs2d_map.h"
+#include "gs2d_depth_rule.h"
 #include <math.h>
 #include <stdio.h>
 
@@ -139,21 +141,6 @@ template <typename T> __device__ __forceinline__ void quaternion_to_matrix(T r, 
     R[0] = T(1) - two_s * (j * j + k * k); R[1] = two_s * (i * j - k * r);        R[2] = two_s * (i * k + j * r);
     R[3] = two_s * (i * j + k * r);        R[4] = T(1) - two_s * (i * i + k * k); R[5] = two_s * (j * k - i * r);
     R[6] = two_s * (i * k - j * r);        R[7] = two_s * (j * k + i * r);        R[8] = T(1) - two_s * (i * i + j * j);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------- depth
-struct DepthCfg { int use_weight_norm; float eps, near, far; };
-
-// The depth of a rendered view (render/__init__.py:129-132): D / (A + eps), zero outside [near, far]; D itself without
-// use_weight_norm.  A NaN passes through.
-__device__ __forceinline__ float normalised_depth(const DepthCfg& c, float D, float A)
-{
-    float d = D;
-    if (c.use_weight_norm) {
-        d = D / (A + c.eps);
-        if (d > c.far || d < c.near) d = 0.f;
-    }
-    return d;
 }
 
 // ----------------------------------------------------------------------------------------------------------------- reductions

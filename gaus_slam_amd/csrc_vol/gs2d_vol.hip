@@ -1,7 +1,7 @@
 // Block-hashed TSDF volume on the device (include/gs2d_vol.h, which states every definition): the volume of include/gs2d_tsdf.h
 // stored as 8 x 8 x 8 voxel blocks behind a hash table, allocated on demand from the depth images.  The integration rule and the
-// tetrahedron table are RESTATED here from csrc_map/gs2d_tsdf.hip -- that file belongs to the map library's pinned source hash --
-// and tests/test_gpu_vol.py compares the two bit for bit.
+// tetrahedron table are shared with the dense volume through ../csrc_map/gs2d_tsdf_rule.h; tests/test_gpu_vol.py holds this
+// volume's storage, allocation and extraction to the dense volume bit for bit.
 //
 //   vol_allocate_kernel:  one thread per pixel: the world point, its range of blocks, equal ranges of neighbouring lanes
 //                         collapsed, then one insert per block.
@@ -18,6 +18,7 @@
 // stores and read by later launches only.  No spin loops, no flags, no fences.
 #include "../csrc/gs2d_scan.h"
 #include "../../include/gs2d_vol.h"
+#include "../csrc_map/gs2d_tsdf_rule.h"
 #include <math.h>
 #include <stdio.h>
 
@@ -122,23 +123,7 @@ __device__ __forceinline__ int find_slot(const uint64_t* __restrict__ tkeys, con
     return -1;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------- depth
-struct DepthCfg { int use_weight_norm; float eps, near, far; };
-
-// The depth of a rendered view, as gs2d_tsdf_integrate takes it: D / (A + eps), zero outside [near, far]; D itself without
-// use_weight_norm.  A NaN passes through.
-__device__ __forceinline__ float normalised_depth(const DepthCfg& c, float D, float A)
-{
-    float d = D;
-    if (c.use_weight_norm) {
-        d = D / (A + c.eps);
-        if (d > c.far || d < c.near) d = 0.f;
-    }
-    return d;
-}
-
 struct Lattice { float ox, oy, oz, L; };
-struct Frame { int W, H; float fx, fy, cx, cy, sdf_trunc, depth_trunc; int allmap, rgb8; };
 
 // ------------------------------------------------------------------------------------------------------------------- allocate
 __global__ void __launch_bounds__(256)
@@ -186,18 +171,6 @@ __global__ void __launch_bounds__(256) vol_insert_kernel(int n, const uint64_t* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------ integrate
-// max over the block (centre c, half extents h) of the plane  a . p + a3,  plus a slack of 1e-4 of the magnitudes that went
-// into it, as in the dense volume's kernel: a block is only skipped when every voxel in it is skipped by the per-voxel rules.
-__device__ __forceinline__ bool brick_outside(const float a[4], const float mag[4], const float c[3], const float h[3])
-{
-    const float val = ((a[0] * c[0] + a[1] * c[1]) + a[2] * c[2]) + a[3];
-    const float reach = (fabsf(a[0]) * h[0] + fabsf(a[1]) * h[1]) + fabsf(a[2]) * h[2];
-    const float size = ((mag[0] * (fabsf(c[0]) + h[0]) + mag[1] * (fabsf(c[1]) + h[1])) + mag[2] * (fabsf(c[2]) + h[2])) + mag[3];
-    return val + reach < -1e-4f * size;  // false for a NaN: the block is then kept
-}
-
-__device__ __forceinline__ float running_average(float old, float w, float x) { return (old * w + x) / (w + 1.f); }
-
 __global__ void __launch_bounds__(256)
 vol_integrate_kernel(Lattice G, Frame F, DepthCfg dc, int capacity, const float* __restrict__ w2c, const float* __restrict__ color,
                      const float* __restrict__ depth, float* __restrict__ pool, const uint64_t* __restrict__ keys,
@@ -218,57 +191,21 @@ vol_integrate_kernel(Lattice G, Frame F, DepthCfg dc, int capacity, const float*
             h[j] = 0.5f * (float)B * G.L;
             c[j] = org[j] + (float)(B * b[j]) * G.L + h[j];
         }
-        const float W = (float)F.W, H = (float)F.H, far = F.depth_trunc + F.sdf_trunc;
-        const float ku0 = F.cx + 0.5f, ku1 = ku0 - W, kv0 = F.cy + 0.5f, kv1 = kv0 - H;
-        float a[6][4], g[6][4];  // a voxel is updated only where all six planes are > 0 (>= 0 for the left and top ones)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float X = m[j], Y = m[4 + j], Z = m[8 + j];
-            a[0][j] = Z;                          g[0][j] = fabsf(Z);
-            a[1][j] = (j == 3 ? far : 0.f) - Z;   g[1][j] = fabsf(Z) + (j == 3 ? far : 0.f);
-            a[2][j] = F.fx * X + ku0 * Z;         g[2][j] = fabsf(F.fx * X) + fabsf(ku0 * Z);
-            a[3][j] = -(F.fx * X + ku1 * Z);      g[3][j] = fabsf(F.fx * X) + fabsf(ku1 * Z);
-            a[4][j] = F.fy * Y + kv0 * Z;         g[4][j] = fabsf(F.fy * Y) + fabsf(kv0 * Z);
-            a[5][j] = -(F.fy * Y + kv1 * Z);      g[5][j] = fabsf(F.fy * Y) + fabsf(kv1 * Z);
-        }
-        bool out = false;
-#pragma unroll
-        for (int p = 0; p < 6; p++) out = out || brick_outside(a[p], g[p], c, h);
-        if (out) return;
+        if (outside_frustum(F, m, c, h)) return;
     }
     const size_t plane = (size_t)capacity * BV, base = (size_t)slot * BV;
-    const size_t HW = (size_t)F.W * F.H;
     for (int l = threadIdx.x; l < BV; l += 256) {
         const int ix = B * b[0] + (l & 7), iy = B * b[1] + ((l >> 3) & 7), iz = B * b[2] + (l >> 6);
         const float px = G.ox + ((float)ix + 0.5f) * G.L, py = G.oy + ((float)iy + 0.5f) * G.L, pz = G.oz + ((float)iz + 0.5f) * G.L;
-        const float qz = ((m[8] * px + m[9] * py) + m[10] * pz) + m[11];
-        if (!(qz > 0.f)) continue;
-        const float qx = ((m[0] * px + m[1] * py) + m[2] * pz) + m[3];
-        const float qy = ((m[4] * px + m[5] * py) + m[6] * pz) + m[7];
-        const float uf = ((qx * F.fx) / qz + F.cx) + 0.5f, vf = ((qy * F.fy) / qz + F.cy) + 0.5f;
-        if (!(uf >= 0.f && uf < (float)F.W && vf >= 0.f && vf < (float)F.H)) continue;
-        const int u = (int)uf, v = (int)vf;  // 0 <= u < W, 0 <= v < H: the bounds of every image read below
-        const size_t pix = (size_t)v * F.W + u;
-        const float d = F.allmap ? normalised_depth(dc, depth[pix], depth[HW + pix]) : depth[pix];
-        if (!(d > 0.f && d <= F.depth_trunc)) continue;
-        const float xn = ((float)u - F.cx) / F.fx, yn = ((float)v - F.cy) / F.fy;
-        const float sdf = (d - qz) * sqrtf((1.f + xn * xn) + yn * yn);
-        if (!(sdf > -F.sdf_trunc)) continue;
-        const float tn = fminf(1.f, sdf / F.sdf_trunc);
-        float c[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            float x = fminf(fmaxf(color[ch * HW + pix], 0.f), 1.f);  // fmaxf drops a NaN: it counts as 0
-            if (F.rgb8) x = (float)(int)(x * 255.f) / 255.f;
-            c[ch] = x;
-        }
-        const size_t lin = base + l;  // slot < capacity, l < 512: inside every plane
-        const float w = pool[plane + lin];
-        pool[lin] = running_average(pool[lin], w, tn);
-        pool[2 * plane + lin] = running_average(pool[2 * plane + lin], w, c[0]);
-        pool[3 * plane + lin] = running_average(pool[3 * plane + lin], w, c[1]);
-        pool[4 * plane + lin] = running_average(pool[4 * plane + lin], w, c[2]);
-        pool[plane + lin] = w + 1.f;
+        voxel_sample(F, dc, m, px, py, pz, color, depth, [&](float tn, const float c[3]) {
+            const size_t lin = base + l;  // slot < capacity, l < 512: inside every plane
+            const float w = pool[plane + lin];
+            pool[lin] = running_average(pool[lin], w, tn);
+            pool[2 * plane + lin] = running_average(pool[2 * plane + lin], w, c[0]);
+            pool[3 * plane + lin] = running_average(pool[3 * plane + lin], w, c[1]);
+            pool[4 * plane + lin] = running_average(pool[4 * plane + lin], w, c[2]);
+            pool[plane + lin] = w + 1.f;
+        });
     }
 }
 
@@ -296,76 +233,6 @@ vol_copy_kernel(int to_dense, Box X, float* dense, int capacity, uint32_t mask, 
 }
 
 // -------------------------------------------------------------------------------------------------------------------- extract
-// The 6 x 16 cases of gs2d_tsdf.h's rule, built at compile time.
-constexpr int TET_AXES[6][2] = {{0, 1}, {0, 2}, {1, 0}, {1, 2}, {2, 0}, {2, 1}};
-constexpr int TET_DET[6] = {+1, -1, -1, +1, +1, -1};
-
-constexpr uint64_t tet_case(int tet, int mask)
-{
-    const int c[4] = {0, 1 << TET_AXES[tet][0], (1 << TET_AXES[tet][0]) | (1 << TET_AXES[tet][1]), 7};
-    int in[4] = {0, 0, 0, 0}, out[4] = {0, 0, 0, 0}, ni = 0, no = 0;
-    for (int k = 0; k < 4; k++) {
-        if ((mask >> k) & 1) in[ni++] = k; else out[no++] = k;
-    }
-    if (ni == 0 || ni == 4) return 0;
-    int inv = 0;
-    for (int i = 0; i < ni; i++)
-        for (int o = 0; o < no; o++) inv += out[o] < in[i] ? 1 : 0;
-    const bool flip = (TET_DET[tet] > 0) == ((inv & 1) != 0);
-    int e[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, nt = 1;  // the edges [p, q] of the vertices the triangles use
-    if (ni == 1) {
-        for (int j = 0; j < 3; j++) { e[j][0] = in[0]; e[j][1] = out[j]; }
-    } else if (ni == 3) {
-        for (int j = 0; j < 3; j++) { e[j][0] = in[j]; e[j][1] = out[0]; }
-    } else {
-        nt = 2;
-        e[0][0] = in[0]; e[0][1] = out[0];
-        e[1][0] = in[0]; e[1][1] = out[1];
-        e[2][0] = in[1]; e[2][1] = out[1];
-        e[3][0] = in[1]; e[3][1] = out[0];
-    }
-    const int tri[2][3] = {{0, flip ? 2 : 1, flip ? 1 : 2}, {0, flip ? 3 : 2, flip ? 2 : 3}};
-    uint64_t r = (uint64_t)nt;
-    for (int i = 0; i < nt; i++)
-        for (int j = 0; j < 3; j++) {
-            const int p = e[tri[i][j]][0], q = e[tri[i][j]][1];
-            const int lo = p < q ? p : q, hi = p < q ? q : p;  // corner codes grow with the corner number: the lower one owns
-            r |= (uint64_t)(c[lo] | (c[hi] << 3)) << (4 + 6 * (3 * i + j));
-        }
-    return r;
-}
-
-struct TetTable { uint64_t e[6 * 16]; };
-constexpr TetTable make_tet_table()
-{
-    TetTable t{};
-    for (int k = 0; k < 6; k++)
-        for (int m = 0; m < 16; m++) t.e[16 * k + m] = tet_case(k, m);
-    return t;
-}
-constexpr TetTable TET_HOST = make_tet_table();
-__constant__ TetTable TET = make_tet_table();
-
-// the edge kind of a corner-code difference: +x 1, +y 2, +z 4, +xy 3, +yz 6, +xz 5, +xyz 7
-__device__ __forceinline__ int edge_kind(int diff) { return (int)((0x64523100u >> (4 * diff)) & 7u); }
-// kind -> corner code of the other end: 1, 2, 4, 3, 6, 5, 7
-__device__ __forceinline__ int kind_code(int kind) { return (int)((0x7563421u >> (4 * kind)) & 7u); }
-
-__device__ __forceinline__ int tet_mask(uint32_t bits, int k)
-{
-    const int c1 = 1 << TET_AXES[k][0], c2 = c1 | (1 << TET_AXES[k][1]);
-    return (int)((bits & 1u) | (((bits >> c1) & 1u) << 1) | (((bits >> c2) & 1u) << 2) | (((bits >> 7) & 1u) << 3));
-}
-
-__device__ __forceinline__ uint32_t cube_triangles(uint32_t bits)
-{
-    if (bits == 0u || bits == 0xFFu) return 0;
-    uint32_t n = 0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) n += (uint32_t)(TET.e[16 * k + tet_mask(bits, k)] & 3u);
-    return n;
-}
-
 // The neighbourhood of a block in LDS: voxels -1 .. 8 per axis (N = 10), cubes -1 .. 7 (C = 9).
 constexpr int N = B + 2, NV = N * N * N, C = B + 1, NC = C * C * C;
 struct Hood {
@@ -508,8 +375,6 @@ __global__ void __launch_bounds__(SCAN_T) vol_scan_kernel(uint32_t* sums, int st
     __syncthreads();
     scan_blocksums_body(sums + stride, nblk, header + GS2D_VOL_WS_TRIANGLES, nullptr);
 }
-
-struct MeshOut { float* vertices; float* colors; int32_t* triangles; uint32_t V, T; };
 
 __global__ void __launch_bounds__(256)
 vol_write_kernel(Tables T, Lattice G, const uint8_t* __restrict__ masks, const uint16_t* __restrict__ rank,

@@ -20,8 +20,8 @@
  *
  * ------------------------------------------------------------------------------------------------------------------- mesh ids
  * key [H,W] uint64 of a mesh (vertices [V,3] float32, triangles [T,3] int32), 0 < near <= far.  Camera transform, setup, the
- * skip rules, the COVERED test, the depth z and the COUNTS test are VERBATIM those of include/gs2d_mesh.h, restated (this
- * library includes nothing of another):
+ * skip rules, the COVERED test, the depth z and the COUNTS test are VERBATIM those of include/gs2d_mesh.h, and one piece of code
+ * with the mesh library's (shared through gaus_slam_amd/csrc_mesh/gs2d_tri_raster.h):
  *   skipped  an index outside [0, V), or a camera-space coordinate of a vertex that is not finite.
  *   setup    with the camera-space vertices a, b, c:  n0 = b x c, n1 = c x a, n2 = a x b, where p x q = (p.y q.z - p.z q.y,
  *            p.z q.x - p.x q.z, p.x q.y - p.y q.x);  N = (b - a) x (c - a);  num = (N.x a.x + N.y a.y) + N.z a.z;
@@ -36,8 +36,8 @@
  *            triangle index.  GS2D_VIZ_NO_KEY (all ones) where nothing counts.
  * Equal BIT FOR BIT to a brute force over every (triangle, pixel) pair, the same bits in every run (64-bit integer atomicMin,
  * no float atomics), and its high words are the bits gs2d_mesh_render_depth leaves with resolve = 0 (+inf where key is all ones).
- * Culling is gs2d_mesh.h's scheme, restated: one lane per triangle does the setup and finds a pixel rectangle that contains
- * every pixel the definition can cover -- nothing when every z lies outside [near, far]; the whole image when a vertex has
+ * Culling is gs2d_mesh.h's scheme, shared through the same header: one lane per triangle does the setup and finds a pixel
+ * rectangle that contains every pixel the definition can cover -- nothing when every z lies outside [near, far]; the whole image when a vertex has
  * z <= near or the projection is rounding noise (2 eps >= 0.6); else the float64 bounding box of the projected vertices grown
  * by the pad P = 1 + 2 eps w / (1 - 2 eps) of gs2d_mesh.h (derivation: DESIGN.md section 7.9).  A rectangle of at most
  * GS2D_VIZ_SMALL_PIXELS pixels is rasterised by its lane; larger ones by the whole wave, one after another; one of more than

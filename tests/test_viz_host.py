@@ -33,7 +33,8 @@ def test_declared_symbols_are_the_bound_and_the_exported_ones(vizlib):
     from gaus_slam_amd import build, _viz_lib
     names = set(re.findall(r"\b(gs2d_viz_[a-z0-9_]+)\s*\(", abi._code(HEADER)))
     assert names == NAMES == set(abi._prototypes(HEADER))
-    assert list(_viz_lib.ABI) == [HEADER] == [os.path.basename(h) for h in build.VIZ_HEADERS]
+    assert list(_viz_lib.ABI) == [HEADER] and os.path.basename(build.VIZ_HEADERS[0]) == HEADER
+    assert [os.path.basename(h) for h in build.VIZ_HEADERS[1:]] == ["gs2d_tri_raster.h"]
     assert set(_viz_lib.ABI[HEADER]) == names and _viz_lib.VIZ_EXPORTS == list(_viz_lib.ABI[HEADER])
     for n in sorted(names):
         assert hasattr(vizlib, n), n
@@ -81,9 +82,12 @@ def test_defines_hash_and_entry_point(vizlib, monkeypatch):
     build.build()
     assert built == ["viz"]
     monkeypatch.undo()
-    for f in os.listdir(build.CSRC_VIZ):  # it includes nothing of another library
+    for f in os.listdir(build.CSRC_VIZ):  # what it includes of another library is hashed and watched: the mesh library's rasterizer
         text = open(os.path.join(build.CSRC_VIZ, f)).read()
-        assert re.findall(r'^\s*#\s*include\s*"([^"]+)"', text, flags=re.M) == ["../../include/gs2d_viz.h"]
+        includes = re.findall(r'^\s*#\s*include\s*"([^"]+)"', text, flags=re.M)
+        assert includes == ["../../include/gs2d_viz.h", "../csrc_mesh/gs2d_tri_raster.h"]
+        hashed = {os.path.realpath(h) for h in build.VIZ_HEADERS}
+        assert all(os.path.realpath(os.path.join(build.CSRC_VIZ, i)) in hashed for i in includes)
     seen = []
     monkeypatch.setattr(build, "_is_stale", lambda lib_path, source_hash, deps: seen.extend(deps) or False)
     assert build._viz_stale() is False
@@ -103,6 +107,28 @@ def test_a_changed_source_makes_the_library_stale(vizlib, tmp_path, monkeypatch)
     with open(src / "gs2d_viz.hip", "a") as fh:
         fh.write("// one more line\n")
     assert build.viz_source_hash() != before and build._viz_stale() is True
+
+
+def test_the_shared_rasterizer_moves_the_mesh_and_the_viz_hash_only(vizlib, tmp_path, monkeypatch):
+    """csrc_mesh/gs2d_tri_raster.h is compiled into both libraries: a change to it must reach both hashes and no other."""
+    from gaus_slam_amd import build
+    hashes = lambda: (build.mesh_source_hash(), build.viz_source_hash())
+    others = lambda: (build.view_source_hash(), build.ingest_source_hash(), build.front_source_hash(), build.lpips_source_hash(), build.covis_source_hash(),
+                      build.vol_source_hash(), build.loss_source_hash(), build.map_source_hash(), build.gs3d_source_hash(), build.source_hash())
+    before, kept = hashes(), others()
+    assert not build._mesh_stale() and not build._viz_stale()
+    src = tmp_path / "csrc_mesh"
+    shutil.copytree(build.CSRC_MESH, src)
+    shared = [str(src / os.path.basename(h)) for h in build.VIZ_HEADERS[1:]]
+    monkeypatch.setattr(build, "CSRC_MESH", str(src))
+    monkeypatch.setattr(build, "VIZ_HEADERS", build.VIZ_HEADERS[:1] + shared)
+    assert hashes() == before and not build._mesh_stale() and not build._viz_stale()
+    with open(shared[0], "ab") as fh:
+        fh.write(b"\n")
+    after = hashes()
+    assert after[0] != before[0] and after[1] != before[1]
+    assert build._mesh_stale() is True and build._viz_stale() is True
+    assert others() == kept
 
 
 def _with(good, **kv):

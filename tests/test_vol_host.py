@@ -36,7 +36,8 @@ def test_declared_symbols_are_the_bound_and_the_exported_ones(vollib):
     from gaus_slam_amd import build, _vol_lib
     names = set(re.findall(r"\b(gs2d_vol_[a-z0-9_]+)\s*\(", abi._code(HEADER)))
     assert names == NAMES == set(abi._prototypes(HEADER))
-    assert list(_vol_lib.ABI) == [HEADER] == [os.path.basename(h) for h in build.VOL_HEADERS]
+    assert list(_vol_lib.ABI) == [HEADER] and os.path.basename(build.VOL_HEADERS[0]) == HEADER
+    assert [os.path.basename(h) for h in build.VOL_HEADERS[1:]] == ["gs2d_tsdf_rule.h", "gs2d_depth_rule.h"]
     assert set(_vol_lib.ABI[HEADER]) == names and _vol_lib.VOL_EXPORTS == list(_vol_lib.ABI[HEADER])
     for n in sorted(names):
         assert hasattr(vollib, n), n
@@ -83,8 +84,8 @@ def test_every_integer_define_has_its_python_mirror():
 
 # ----------------------------------------------------------------------------------------------------------------------- build
 def test_volume_library_has_a_hash_of_its_own(vollib, monkeypatch):
-    """vol_source_hash() covers csrc_vol/ and gs2d_vol.h only and is the hash in the library; the five hashes are distinct and
-    the four older ones cover what they covered."""
+    """vol_source_hash() covers csrc_vol/, gs2d_vol.h and the two rule headers of csrc_map/ it is compiled with, and is the hash
+    in the library; the five hashes are distinct and the four older ones cover what they covered."""
     from gaus_slam_amd import build, _vol_lib
     dirs = (build.CSRC, build.CSRC_MAP, build.CSRC_MESH, build.CSRC_LOSS, build.CSRC_VOL)
     assert len({os.path.realpath(d) for d in dirs}) == 5
@@ -97,13 +98,18 @@ def test_volume_library_has_a_hash_of_its_own(vollib, monkeypatch):
     assert build.map_source_hash() == build._hash(build.CSRC_MAP, build.MAP_HEADERS)
     assert build.mesh_source_hash() == build._hash(build.CSRC_MESH, build.MESH_HEADERS)
     assert build.loss_source_hash() == build._hash(build.CSRC_LOSS, build.LOSS_HEADERS)
-    for f in os.listdir(build.CSRC_VOL):  # it restates what it needs of the map library: nothing of csrc_map/ is included
+    for f in os.listdir(build.CSRC_VOL):  # of the map library it includes the rule header and nothing else: no error functions, no C ABI
         includes = re.findall(r'^\s*#\s*include\s*[<"]([^>"]+)[>"]', open(os.path.join(build.CSRC_VOL, f)).read(), flags=re.M)
-        assert includes and not [i for i in includes if "csrc_map" in i or "gs2d_tsdf" in i or "gs2d_map" in i], (f, includes)
+        assert [i for i in includes if "csrc_map" in i] == ["../csrc_map/gs2d_tsdf_rule.h"], (f, includes)
+        assert not [i for i in includes if os.path.basename(i) in ("gs2d_map_internal.h", "gs2d_map.h", "gs2d_tsdf.h")], (f, includes)
+    rules = [os.path.join(build.CSRC_MAP, f) for f in ("gs2d_tsdf_rule.h", "gs2d_depth_rule.h")]
+    assert all(os.path.isfile(r) for r in rules) and set(rules) <= set(build.VOL_HEADERS)
+    nested = re.findall(r'^\s*#\s*include\s*"([^"]+)"', open(rules[0]).read(), flags=re.M)
+    assert nested == ["gs2d_depth_rule.h"] and not re.findall(r'^\s*#\s*include\s*"([^"]+)"', open(rules[1]).read(), flags=re.M)
     seen = []
     monkeypatch.setattr(build, "_is_stale", lambda lib_path, source_hash, deps: seen.extend(deps) or False)
     assert build._vol_stale() is False
-    want = set(build.VOL_HEADERS) | {os.path.join(build.CSRC_VOL, f) for f in os.listdir(build.CSRC_VOL)}
+    want = set(build.VOL_HEADERS) | set(rules) | {os.path.join(build.CSRC_VOL, f) for f in os.listdir(build.CSRC_VOL)}
     assert want | {os.path.join(build.CSRC, f) for f in ("gs2d_scan.h", "gs2d_common.h")} <= set(seen)
 
 
@@ -115,7 +121,7 @@ def test_touching_a_volume_source_moves_the_fifth_hash_only(vollib, tmp_path, mo
     assert not build._vol_stale()
     copy = tmp_path / HEADER
     copy.write_bytes(open(build.VOL_HEADERS[0], "rb").read() + b"\n")
-    monkeypatch.setattr(build, "VOL_HEADERS", [str(copy)])
+    monkeypatch.setattr(build, "VOL_HEADERS", [str(copy)] + build.VOL_HEADERS[1:])
     assert build.vol_source_hash() != before and build._vol_stale()
     assert others() == kept
     monkeypatch.undo()
@@ -128,6 +134,30 @@ def test_touching_a_volume_source_moves_the_fifth_hash_only(vollib, tmp_path, mo
             fh.write(b"\n")
         assert build.vol_source_hash() != before, f
         before = build.vol_source_hash()
+    assert others() == kept
+
+
+def test_the_shared_rule_moves_the_map_and_the_volume_hash_only(vollib, tmp_path, monkeypatch):
+    """csrc_map/gs2d_tsdf_rule.h and gs2d_depth_rule.h are compiled into both libraries: a change to either must reach both
+    hashes and no other."""
+    from gaus_slam_amd import build
+    hashes = lambda: (build.map_source_hash(), build.vol_source_hash())
+    others = lambda: (build.loss_source_hash(), build.mesh_source_hash(), build.viz_source_hash(), build.gs3d_source_hash(), build.source_hash())
+    before, kept = hashes(), others()
+    assert not build._map_stale() and not build._vol_stale()
+    src = tmp_path / "csrc_map"
+    shutil.copytree(build.CSRC_MAP, src)
+    shared = [str(src / os.path.basename(h)) for h in build.VOL_HEADERS[1:]]
+    monkeypatch.setattr(build, "CSRC_MAP", str(src))
+    monkeypatch.setattr(build, "VOL_HEADERS", build.VOL_HEADERS[:1] + shared)
+    assert hashes() == before and not build._map_stale() and not build._vol_stale()
+    for path in shared:
+        with open(path, "ab") as fh:
+            fh.write(b"\n")
+        after = hashes()
+        assert after[0] != before[0] and after[1] != before[1], path
+        assert build._map_stale() is True and build._vol_stale() is True
+        before = after
     assert others() == kept
 
 
