@@ -3,7 +3,8 @@ and points), the float32 brute-force nearest neighbour, the statistics with math
 test reference of tests/test_recon_host.py and tests/test_gpu_recon.py and the yardstick of scripts/recon_bench.py.
 
 Two things are NOT taken from the library's way of doing them: nearest() evaluates every pair (no grid), and the sums are plain
-numpy / fsum sums (no workgroup order)."""
+numpy / fsum sums (no workgroup order).  The one exception says so in its name: fixed_order_sum restates exactly that order, for
+the tests that hold the reductions to it bit for bit at the group cap."""
 import math
 
 import numpy as np
@@ -145,6 +146,38 @@ def distance_stats(dist, thr_a, thr_b):
     with np.errstate(invalid="ignore"):
         return dict(count=float(len(fin)), sum=math.fsum(fin), sum_sq=math.fsum(fin * fin), max=float(fin.max()) if len(fin) else 0.0,
                     below_a=float((d < np.float32(thr_a)).sum()), below_b=float((d < np.float32(thr_b)).sum()))
+
+
+def fixed_order_groups(n):
+    """(G, C) of the fixed-order reductions (gs2d_recon_distance_stats, gs2d_recon_pair_sums, gs2d_mesh_depth_l1_sums) over n
+    elements: G = min(256, ceil(n / 256)) workgroups of C = ceil(n / G) rounded up to a multiple of 256 elements each."""
+    G = min(256, -(-n // 256))
+    return G, -(-(-(-n // G)) // 256) * 256
+
+
+def fixed_order_sum(x):
+    """The sum of x [n] or of every column of x [n, k] (float64; 0.0 for an element that is not counted, which changes no partial
+    sum) in the order the headers fix: thread t of workgroup g adds its elements g C + t + 256 j in turn, the 64 lanes of a wave
+    are combined by the xor butterfly 32, 16, ..., 1, the four waves as (r0 + r1) + (r2 + r3), the G partials in index order."""
+    x = np.asarray(x, np.float64)
+    flat = x.reshape(len(x), -1)
+    G, C = fixed_order_groups(len(flat))
+    padded = np.zeros((G * C, flat.shape[1]))
+    padded[:len(flat)] = flat
+    steps = padded.reshape(G, C // 256, 256, -1)
+    acc = np.zeros((G, 256, flat.shape[1]))
+    for j in range(C // 256):
+        acc = acc + steps[:, j]
+    v = acc.reshape(G, 4, 64, -1)
+    lane = np.arange(64)
+    for d in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lane ^ d]
+    assert (v == v[:, :, :1]).all()  # every lane ends with the same bits
+    partial = (v[:, 0, 0] + v[:, 1, 0]) + (v[:, 2, 0] + v[:, 3, 0])
+    total = np.zeros(flat.shape[1])
+    for g in range(G):
+        total = total + partial[g]
+    return total.reshape(x.shape[1:]) if x.ndim > 1 else float(total[0])
 
 
 def inverse_rigid32(transform):

@@ -198,6 +198,38 @@ def test_depth_l1_sums_against_fsum():
     assert table[2].tolist() == [1.0, 2.0]  # gt has no depth there: it counts as 0, as in the reference
 
 
+@pytest.mark.parametrize("n", [65536, 65537, 200003])
+def test_depth_l1_sums_at_the_group_cap(n):
+    """G = 256 workgroups from 65 536 pixels on: C = 256 there (the last size with one element per thread), 512 at 65 537 (the
+    strided loop; the workgroups from the 129th on own nothing, and the last pixel is the only one of its workgroup), 1024 at
+    200 003.  Every 500 x 500 Depth L1 runs here.  The count is exact; the sum equals the header's fixed order restated in float64
+    (recon_ref.fixed_order_sum) bit for bit, and math.fsum within the 1e-12 of the test above."""
+    from gaus_slam_amd import _mesh_lib, meshrender as mr
+    assert recon_ref.fixed_order_groups(n) == (256, {65536: 256, 65537: 512, 200003: 1024}[n])
+    rng = np.random.default_rng(n)
+    gt = rng.uniform(0.5, 6.0, n).astype(np.float32)
+    rec = (gt + rng.normal(0.0, 0.05, n)).astype(np.float32)
+    rec[rng.random(n) < 0.2] = np.inf  # rec holes, unresolved: not counted
+    gt[rng.random(n) < 0.1] = np.inf  # gt holes: 0 where rec has a depth
+    rec[-1], gt[-1] = 1.5, 1.25
+    r0, g0 = np.where(np.isinf(rec), np.float32(0), rec), np.where(np.isinf(gt), np.float32(0), gt)
+    sel = r0 > 0
+    assert 0.7 * n < sel.sum() < 0.9 * n and (sel & (g0 == 0)).sum() > 100 and (~sel & (g0 > 0)).sum() > 100
+    want = recon_ref.fixed_order_sum(np.where(sel, np.abs(g0.astype(np.float64) - r0.astype(np.float64)), 0.0))
+    count, total = ref.depth_l1_sums(r0, g0)
+    table = torch.zeros((2, 2), dtype=torch.float64, device=DEV)
+    recd, gtd = _dev(rec), _dev(gt)
+    mr.depth_l1_sums(recd, gtd, table, 0)
+    mr.depth_l1_sums(_dev(rec), _dev(gt), table, 1)
+    rows = table.cpu().numpy()
+    print(f"n = {n}: device {rows[0].tolist()!r}, fixed order {want!r}, fsum {total!r}, relative difference {abs(rows[0, 1] - total) / total:.2e}")
+    assert np.array_equal(rows[0].view(np.int64), rows[1].view(np.int64))  # two runs: equal bits
+    assert rows[0, _mesh_lib.L1_COUNT] == count == sel.sum()
+    assert rows[0, _mesh_lib.L1_SUM] == want
+    assert abs(rows[0, _mesh_lib.L1_SUM] - total) <= 1e-12 * total
+    assert np.array_equal(_bits(recd.cpu().numpy()), _bits(r0)) and np.array_equal(_bits(gtd.cpu().numpy()), _bits(g0))  # resolved in place
+
+
 def test_depth_l1_against_the_reference_and_with_a_transform():
     from gaus_slam_amd import meshrender as mr
     V, T, V2 = _l1_meshes()

@@ -6,7 +6,9 @@ nearest          dist and index equal the float32 brute force BIT FOR BIT, over 
                  boundary of and up to 100 box sizes outside the targets' box.
 sample_surface   tri equal on every sample the reference does not flag (expected flags in float64: none), points within 8
                  float32 ulps of the largest absolute coordinate.
-statistics       counts equal exactly, sums within 1e-12 relative of math.fsum, the six metrics within 1e-12.
+statistics       counts equal exactly, sums within 1e-12 relative of math.fsum, the six metrics within 1e-12.  At 65 536, 65 537
+                 and 200 003 elements (the cap of 256 workgroups, then the strided loop) the sums of distance_stats and
+                 pair_sums also equal the header's fixed order restated in float64 bit for bit.
 icp_align        T after every iteration within 1000 x the largest entry-wise difference between two runs of the reference that
                  add the pairs in forward and in reversed order (measured on the CPU: 8.66e-14, so 8.66e-11 is allowed),
                  fitness and the iteration count equal exactly.
@@ -334,6 +336,72 @@ def test_pair_sums_against_the_reference():
         assert got[0] == want[0] and (thr == 0.1 or 3 < want[0] < len(src))
         scale = ref.pair_sums(np.abs(src), None, np.abs(dst), dist.cpu().numpy(), index.cpu().numpy(), thr)  # sums of magnitudes
         assert (np.abs(got - want) <= 1e-12 * np.maximum(scale, 1.0) * 4).all(), np.abs(got - want)
+
+
+GROUP_CAP = {65536: 256, 65537: 512, 200003: 1024}  # n -> C: 256 workgroups from 65 536 elements on, then the strided loop
+
+
+@pytest.mark.parametrize("n", list(GROUP_CAP))
+def test_distance_stats_at_the_group_cap(n):
+    """The cap G = 256 and the strided loop C > 256 (at 65 537 the workgroups from the 129th on own nothing and the last
+    element, the maximum, is the only one of its workgroup).  Counts and the maximum exactly; the sums equal the header's fixed
+    order restated in float64 (ref.fixed_order_sum) bit for bit, and math.fsum within 1e-12."""
+    from gaus_slam_amd import _map_lib as S, recon
+    assert ref.fixed_order_groups(n) == (256, GROUP_CAP[n])
+    rng = np.random.default_rng(n)
+    d = np.abs(rng.normal(0.0, 0.01, n)).astype(np.float32)
+    d[rng.random(n) < 0.05] = np.inf  # no finite target / a non-finite query
+    d[[100, 101]] = np.nan, -0.0
+    d[-1] = 0.25
+    thr = (0.01, 0.004)
+    out, again = recon.distance_stats(dev(d), *thr), recon.distance_stats(dev(d), *thr)
+    assert torch.equal(out[:6].view(torch.int64), again[:6].view(torch.int64))
+    got = out[:S.RECON_STATS_VALUES].cpu().numpy()
+    want = ref.distance_stats(d, *thr)
+    assert got[S.RECON_STATS_COUNT] == want["count"] and 0.9 * n < want["count"] < n - 1
+    assert got[S.RECON_STATS_BELOW_A] == want["below_a"] and got[S.RECON_STATS_BELOW_B] == want["below_b"] and 0 < want["below_b"] < want["below_a"]
+    assert got[S.RECON_STATS_MAX] == want["max"] == float(np.float32(0.25))
+    x = np.where(np.isfinite(d), d.astype(np.float64), 0.0)
+    fixed = ref.fixed_order_sum(np.stack([x, x * x], 1))
+    for k, name, f in ((S.RECON_STATS_SUM, "sum", fixed[0]), (S.RECON_STATS_SUM_SQ, "sum_sq", fixed[1])):
+        rel = abs(got[k] - want[name]) / want[name]
+        print(f"n = {n} {name}: device {got[k]!r}, fixed order {f!r}, fsum {want[name]!r}, relative difference {rel:.2e}")
+        assert got[k] == f and rel <= 1e-12
+
+
+@pytest.mark.parametrize("n", list(GROUP_CAP))
+def test_pair_sums_at_the_group_cap(n):
+    """The 17 sums of an ICP step over n queries, a transform inside the kernel and a threshold that leaves pairs out: n exactly,
+    every sum bit for bit in the header's fixed order, and within 1e-12 of math.fsum relative to the sum of the magnitudes (the
+    bound of test_pair_sums_against_the_reference)."""
+    import math
+    from gaus_slam_amd import _map_lib, recon
+    assert ref.fixed_order_groups(n) == (256, GROUP_CAP[n])
+    src0, dst, _ = ref.icp_case(3000, 5000)
+    rng = np.random.default_rng(n)
+    src = (src0[rng.integers(0, len(src0), n)] + rng.normal(0.0, 0.01, (n, 3))).astype(np.float32)
+    src[7] = np.nan  # a non-finite query: index -1, left out
+    M = ref.rigid((1, 0.2, 0.1), 1.0, (0.01, 0.0, -0.01)).astype(np.float32)
+    thr = 0.02
+    grid = recon.PointGrid(dev(dst))
+    dist, index = grid.nearest(dev(src), dev(M))
+    got = grid.pair_sums(dev(src), dist, index, thr, dev(M))[:_map_lib.RECON_PAIR_VALUES].cpu().numpy()
+    again = grid.pair_sums(dev(src), dist, index, thr, dev(M))[:_map_lib.RECON_PAIR_VALUES].cpu().numpy()
+    assert np.array_equal(got.view(np.int64), again.view(np.int64))
+    d, i = dist.cpu().numpy(), index.cpu().numpy()
+    with np.errstate(invalid="ignore"):
+        sel = (i >= 0) & (d < np.float32(thr))
+    assert i[7] == -1 and 0.2 * n < sel.sum() < 0.9 * n and sel[-1000:].any()
+    p, q, dd = ref.transform_points(src, M).astype(np.float64), dst[np.where(sel, i, 0)].astype(np.float64), d.astype(np.float64)
+    cols = np.concatenate([np.ones((n, 1)), p, q, (p[:, :, None] * q[:, None, :]).reshape(n, 9), (dd * dd)[:, None]], 1)
+    cols = np.where(sel[:, None], cols, 0.0)
+    fixed = ref.fixed_order_sum(cols)
+    exact = np.array([math.fsum(c) for c in cols.T])
+    scale = np.array([math.fsum(np.abs(c)) for c in cols.T])
+    print(f"n = {n}: {int(sel.sum())} pairs, largest |device - fsum| / scale {float((np.abs(got - exact) / np.maximum(scale, 1.0)).max()):.2e}")
+    assert got[0] == sel.sum()
+    assert np.array_equal(got.view(np.int64), fixed.view(np.int64)), np.flatnonzero(got != fixed)
+    assert (np.abs(got - exact) <= 1e-12 * np.maximum(scale, 1.0) * 4).all(), np.abs(got - exact)
 
 
 def test_icp_align_follows_the_reference_iteration_by_iteration():
